@@ -17,6 +17,9 @@ gating gives (trainer.py:192-221: SSL heads every RS.EPOCH_STEP-th epoch, CM hea
 over the all-gathered global batch: config C3).
 `--graph auto` (Trainer(graph_steps="auto")): per-GPU batches <= 128 replay the step as a hipGraph (the eager step is host-enqueue
 bound there), and so do the steps with the cross-modality head at any batch (600+ small launches); the rest runs eager.
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what the headline figure does not need:
+the instrumented kernel-timing pass behind `roofline`, `projected_strong_scaling`, the weak-scaling leg (N > 1), the CPU-oracle
+baseline and the untimed busy tail.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -112,6 +115,30 @@ def cpu_baseline(batch_sizes, steps: int, budget_s: float = 30.0, threads=(8, 16
                           best["batch"], best["threads"], cores, lo, hi, ORACLE_OVER_REFERENCE_EQUAL_CORES)}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(path, losses, model):
+    """--dump-outputs: what the last timed step computed, as .npy files a later build can be compared with element for element —
+    the losses the step returned (loss.<kind>.npy, float64) and the parameters and floating-point buffers it left behind
+    (state.<name>.npy, float32 / float64).  Above DUMP_BUDGET_BYTES in all, every state tensor keeps the same fraction of its
+    elements: a fixed, seeded sample of its flattened positions (sorted), identical from run to run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss." + k: np.asarray([float(v)], dtype=np.float64) for k, v in losses.items()}
+    state = [(n, t.detach()) for n, t in list(model.named_parameters()) + list(model.named_buffers()) if t.is_floating_point()]
+    size = lambda t: t.numel() * (8 if t.dtype == torch.float64 else 4)
+    frac = min(1.0, (DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values())) / max(sum(size(t) for _, t in state), 1))
+    for n, t in state:
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).reshape(-1)
+        if frac < 1.0:
+            k = max(1, int(t.numel() * frac))
+            t = t[torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values]
+        arrays["state." + n] = t.numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -145,8 +172,13 @@ def main():
                          "lengths, token counts and ids every step, so the per-batch host work (layout spec, table refill, label "
                          "blocks) and the capacity logic of captured graphs are inside the timed region (ADVICE r4)")
     ap.add_argument("--min-busy-seconds", type=float, default=2.0,
-                    help="after the K timed steps, keep stepping (untimed) until the GPU has been busy this long in total, so "
-                         "that a short --steps run is visible to an external utilisation sampler")
+                    help="--full: after the K timed steps, keep stepping (untimed) until the GPU has been busy this long in total, "
+                         "so that a short --steps run is visible to an external utilisation sampler")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the kernel-timing pass (roofline), "
+                         "projected_strong_scaling, the weak-scaling leg (N > 1), the CPU-oracle baseline, the busy tail")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (its losses; the parameters and buffers it left) as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -217,17 +249,18 @@ def main():
                 for i in range(max(args.distinct_batches, 1))]
         return batch_sets[per_gpu_batch]
 
-    def measure(per_gpu_batch, steps, warmup, with_events, busy=False):
+    def measure(per_gpu_batch, steps, warmup, with_events, busy=False, dump_dir=None):
         """W untimed + K timed steps at one per-GPU batch, cycling through the distinct batches (a replayed graph receives each
         as a device-to-device copy into its static inputs — the stand-in for a loader that assembles the next batch there);
-        returns (seconds, max over ranks; family statistics)."""
+        returns (seconds, max over ranks; family statistics).  dump_dir: dump_outputs of the last timed step."""
         pairs = batches_of(per_gpu_batch)
         it = [0]
+        last = [None]
 
         def step():
             batch, meta = pairs[it[0] % len(pairs)]
             it[0] += 1
-            trainer.training_step(batch, meta=meta, cur_epoch=ep)
+            last[0] = trainer.training_step(batch, meta=meta, cur_epoch=ep)
 
         # Untimed, before the W warm-up steps: every distinct batch is stepped once (its row-bucket shapes reach the caching
         # allocator for the first time there, a hipMalloc each) — in graph mode graph_warmup + 1 times, so that the captures the
@@ -248,6 +281,8 @@ def main():
         dt = time.perf_counter() - t0
         measure.captures_in_timed_region = trainer.graph_captures - captures0
         trainer.check_device_flags()              # the padding guards of the compact forms (raises if one tripped)
+        if dump_dir:
+            dump_outputs(dump_dir, last[0], model)
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -278,13 +313,14 @@ def main():
             sync()
         return float(t), stats
 
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     # The timed region runs the product configuration: on cls steps the forward's independent branches (and their backward
     # passes) share the chip on side HIP streams, per-GPU batches <= 128 replay a hipGraph.  Kernel timings for the roofline
     # object come from a SEPARATE instrumented pass of eager ONE-STREAM steps run right after it (same process, same data,
     # same kernels): HIP events bracket a launch on its stream, and a launch that shares the chip with another stream's
     # kernels — or is a node of a replayed graph — has no duration of its own to bracket.
-    dt, fam_stats = measure(args.batch, args.steps, args.warmup, False, busy=True)
+    dt, fam_stats = measure(args.batch, args.steps, args.warmup, False, busy=args.full,
+                            dump_dir=args.dump_outputs if rank == 0 else None)
     timed_captures, live_graphs = getattr(measure, "captures_in_timed_region", 0), len(trainer._graphs)
     first_touch_steps = getattr(measure, "first_touch_steps", 0)
     events_steps, events_dt, events_note = args.steps, dt, None
@@ -304,7 +340,7 @@ def main():
     # measures the real curve.
     projection = None
     # (also skipped by --no-kernel-timing: the lean form the A/B and profiling tools run)
-    if world == 1 and scaling == "strong" and not (args.no_projection or args.no_kernel_timing) and args.batch == args.global_batch \
+    if args.full and world == 1 and scaling == "strong" and not (args.no_projection or args.no_kernel_timing) and args.batch == args.global_batch \
             and args.batch % 8 == 0:
         projection = {}
         for n_gpu in (2, 4, 8):
@@ -315,7 +351,7 @@ def main():
                                       "hip_graph_captures_in_timed_region": getattr(measure, "captures_in_timed_region", 0) if graphed_at(b) else None,
                                       "speedup_ceiling": round((dt / args.steps) / (pdt / psteps), 2)}
     weak = None
-    if world > 1 and scaling == "strong" and not args.no_weak:
+    if args.full and world > 1 and scaling == "strong" and not args.no_weak:
         wsteps = max(10, min(args.steps // 4, 50))
         wdt, _ = measure(args.global_batch, wsteps, 3, False)
         weak = {"per_gpu_batch": args.global_batch, "global_batch": args.global_batch * world, "steps": wsteps,
@@ -459,7 +495,7 @@ def main():
         if projection is not None:
             out["projected_strong_scaling"] = dict(projection, what="one-GPU measurement of the per-GPU step at batch 256 / N; speedup_ceiling = "
                                                    "ms(256) / ms(256 / N) = the N-GPU strong-scaling speed-up with free collectives")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline([int(b) for b in str(args.cpu_batch).split(",") if b], args.cpu_steps)
         print(json.dumps(out), flush=True)
     if world > 1:

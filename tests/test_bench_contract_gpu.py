@@ -1,5 +1,6 @@
-"""bench.py's output contract (one JSON line on stdout with the keys the driver reads), on a short run: default workload
-(eager, batch 256) incl. the roofline and cpu_baseline objects, and a graph-replayed small-batch run."""
+"""bench.py's output contract (one JSON line on stdout with the keys the driver reads), on a short run: the plain line and its
+--dump-outputs files, the --full line of the default workload (eager, batch 256) incl. the roofline and cpu_baseline objects,
+and a graph-replayed small-batch run."""
 import json
 import os
 import subprocess
@@ -23,8 +24,29 @@ def _run(*args):
     return json.loads(lines[0])
 
 
+def test_plain_line_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run measures only the headline: no roofline / projection / CPU baseline; --dump-outputs writes the last timed
+    step's losses and the state it left as float32 / float64 .npy files within the 64 MB budget."""
+    import numpy as np
+    d = _run("--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "bf16" and d["unit"] == "pairs/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) <= 1e-2 * d["value"]
+    assert not any(k in d for k in ("roofline", "cpu_baseline", "projected_strong_scaling", "weak"))
+    files = sorted(os.listdir(tmp_path))
+    assert "loss.cls.npy" in files and "state.mlp_classifier.fc4.weight.npy" in files, files[:10]
+    total = 0
+    for f in files:
+        a = np.load(os.path.join(tmp_path, f))
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
+        total += a.nbytes
+    assert total <= 64e6
+    assert 0 < float(np.load(os.path.join(tmp_path, "loss.cls.npy"))[0]) < 10
+
+
 def test_default_line_has_the_contract_keys():
-    d = _run("--steps", "4", "--warmup", "2", "--cpu-steps", "1")
+    d = _run("--full", "--steps", "4", "--warmup", "2", "--cpu-steps", "1")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -57,7 +79,7 @@ def test_default_line_has_the_contract_keys():
 
 
 def test_small_batch_line_replays_a_graph_and_says_so():
-    d = _run("--batch", "32", "--steps", "6", "--warmup", "4", "--no-cpu-baseline")
+    d = _run("--full", "--batch", "32", "--steps", "6", "--warmup", "4", "--no-cpu-baseline")
     assert d["config"]["hip_graph"] is True and d["scaling"] == "weak" and d["config"]["per_gpu_batch"] == 32
     assert "eager one-stream steps" in d["roofline"]["timing_source"] and "replays a hipGraph" in d["roofline"]["timing_source"]
     assert "cpu_baseline" not in d
@@ -83,8 +105,8 @@ def test_two_rank_launch_line_over_gloo_on_one_gpu():
             port = s.getsockname()[1]
         import signal
         p = subprocess.Popen([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                              "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
-                              "--warmup", "3", "--min-busy-seconds", "0.5"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                              "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps",
+                              "6", "--warmup", "3", "--min-busy-seconds", "0.5"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                              env=env, cwd=ROOT, start_new_session=True)        # own process group: a timeout takes the ranks down too
         try:
             out, err = p.communicate(timeout=300)

@@ -40,7 +40,7 @@ fetch_files, write_files = args[0].split(","), args[1].split(",")
 fetches = [load(f, "FETCH_SIZE") for f in fetch_files if f]
 writes = [load(f, "WRITE_SIZE") for f in write_files if f]
 from druglamp_amd.build import csrc_hash
-summary = {"command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python bench.py --steps 2 --warmup 1 "
+summary = {"command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python bench.py --full --steps 2 --warmup 1 "
                       "--no-cpu-baseline --no-kernel-timing (separate passes per counter; %d + %d passes)" % (len(fetches), len(writes)),
            "correction": "FETCH_SIZE, WRITE_SIZE in KiB; FETCH_SIZE doubled (gfx950 reports 1/2 of wide coalesced reads, "
                          "MI355X_MICROARCH.md section HBM)",
