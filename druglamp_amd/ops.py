@@ -361,7 +361,9 @@ def cast(src: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 def attn_fwd(q, k, v, *, n_problems, n_heads, n_segments, partner_shift, Lq, Lk, head_dim, scale,
              q_strides, k_strides, v_strides, out, o_strides, o_ss, need_lse=True, raw_logits=None, algo=0, key_tail=None):
     """Strides are (problem, head, row) in elements.  Returns the LSE tensor (or None).
-    key_tail = (rows, weight): the last `rows` keys each stand for `weight` identical keys (dl_attn_fwd_args.key_tail_rows)."""
+    key_tail = (rows, weight): the last `rows` keys each stand for `weight` identical keys (dl_attn_fwd_args.key_tail_rows);
+    raw_logits of such a key then hold scale * q.k + log(weight), the logit the softmax uses (a softmax over a raw row gives
+    the weights of the distinct keys; GuidedCrossAttentionFn asks for no raw logits with key_tail)."""
     _need_gpu(q, k, v, out)
     a = AttnFwdArgs()
     a.Q, a.K, a.V, a.O = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
