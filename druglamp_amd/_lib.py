@@ -12,10 +12,14 @@ import torch  # noqa: F401  (must be imported BEFORE the dlopen below: the libra
 #                            torch already loaded instead of bringing up a second, device-less copy)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# DL_USE_STUDY_LIB=1 (tools/ only) loads the -DDL_STUDY build, the only one that reads study switches from the environment
-_study = os.environ.get("DL_USE_STUDY_LIB", "")
-LIB_PATH = os.path.join(_HERE, "lib", "libdruglamp_hip_study.so" if _study == "1" else _study if _study.endswith(".so")   # (a named variant build: same-box A/B of compile-time choices, tools only)
-                        else "libdruglamp_hip.so")
+# DL_USE_STUDY_LIB=libdruglamp_hip_<variant>.so (tools only) loads a named variant build (python -m druglamp_amd.build --variant):
+# same-box A/B of compile-time choices.  The library itself reads no environment.
+_variant = os.environ.get("DL_USE_STUDY_LIB", "")
+if _variant and not _variant.endswith(".so"):
+    raise RuntimeError("DL_USE_STUDY_LIB=%s: the -DDL_STUDY build (libdruglamp_hip_study.so) was removed; commit 97fb613 is the last "
+                       "that builds it (python -m druglamp_amd.build --study).  Only a variant library name (libdruglamp_hip_<variant>.so) "
+                       "is accepted." % _variant)
+LIB_PATH = os.path.join(_HERE, "lib", _variant or "libdruglamp_hip.so")
 
 DL_F32, DL_BF16 = 0, 1
 

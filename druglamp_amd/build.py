@@ -2,9 +2,8 @@
 
     python -m druglamp_amd.build        # incremental
     python -m druglamp_amd.build -f     # force rebuild
-    python -m druglamp_amd.build --study   # additionally libdruglamp_hip_study.so (-DDL_STUDY: reads the tile-study /
-                                           # timing-decomposition switches from the environment; tools/ only, loaded with
-                                           # DL_USE_STUDY_LIB=1 — the product library never reads the environment)
+    python -m druglamp_amd.build --variant NAME -DX=1   # tools only: libdruglamp_hip_NAME.so built with extra -D flags,
+                                                        # loaded with DL_USE_STUDY_LIB=libdruglamp_hip_NAME.so
 
 The shared object lands in druglamp_amd/lib/ (git-ignored; it travels to the GPU box with the
 gpurun snapshot).  No cmake, no torch extension machinery: the C ABI has no torch types.
@@ -93,14 +92,12 @@ def _compile(src, force, objdir=OBJDIR, extra=()):
     return obj
 
 
-def build(force: bool = False, verbose: bool = True, study: bool = False, variant: str = "", defines=()) -> str:
+def build(force: bool = False, verbose: bool = True, variant: str = "", defines=()) -> str:
     """variant (tools only): a product-flavoured library under another name built with extra -D flags, loaded with
     DL_USE_STUDY_LIB=libdruglamp_hip_<variant>.so — same-box A/B of compile-time choices."""
-    objdir = OBJDIR + ("_study" if study else "") + ("_" + variant if variant else "")
-    lib = LIB.replace(".so", "_study.so") if study else LIB
-    if variant:
-        lib = LIB.replace(".so", "_%s.so" % variant)
-    extra = (("-DDL_STUDY",) if study else ()) + tuple(defines)
+    objdir = OBJDIR + ("_" + variant if variant else "")
+    lib = LIB.replace(".so", "_%s.so" % variant) if variant else LIB
+    extra = tuple(defines)
     os.makedirs(objdir, exist_ok=True)
     srcs = _sources()
     with ThreadPoolExecutor(max_workers=min(6, len(srcs))) as ex:
@@ -122,9 +119,11 @@ def _link(LIB, objs, force, verbose):
 
 
 if __name__ == "__main__":
+    _args = sys.argv[1:]
+    _unknown = [a for i, a in enumerate(_args) if a not in ("-f", "--variant") and not a.startswith("-D") and (i == 0 or _args[i - 1] != "--variant")]
+    if _unknown:     # (--study built the -DDL_STUDY library through commit 97fb613; that build was removed)
+        sys.exit("druglamp_amd.build: unknown argument(s) %s (usage: [-f] [--variant NAME -DX=1 ...])" % " ".join(_unknown))
     if "--variant" in sys.argv:              # python -m druglamp_amd.build --variant nt7 -DDL_NT_MASK=7
         build(force="-f" in sys.argv, variant=sys.argv[sys.argv.index("--variant") + 1], defines=[a for a in sys.argv if a.startswith("-D")])
         sys.exit(0)
     build(force="-f" in sys.argv)
-    if "--study" in sys.argv:
-        build(force="-f" in sys.argv, study=True)

@@ -1385,20 +1385,35 @@ int launch_bwd(const AttnP& p, hipStream_t s) {
     const int64_t rows = (int64_t)p.S * p.P * p.H * p.Lq;
     hipLaunchKernelGGL((attn_delta_kernel<T, HD>), dim3((uint32_t)((rows + 15) / 16)), dim3(256), 0, s, p);
   }
-  if constexpr (sizeof(T) == 2 && HD == 128) {
+  if constexpr (sizeof(T) == 2 && HD == 128) {          // ring kernels
     if (p.tail_start < p.Lk) {              // key multiplicities (PGCA on the distinct drug rows)
       hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<T, HD, QT, true>), gq, dim3(ATT_THREADS), 0, s, p);
       hipLaunchKernelGGL((attn_bwd_dkv_ring_kernel<T, HD, KT, true>), gk, dim3(ATT_THREADS), 0, s, p);
-      return DL_OK;
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<T, HD, QT>), gq, dim3(ATT_THREADS), 0, s, p);
+      hipLaunchKernelGGL((attn_bwd_dkv_ring_kernel<T, HD, KT>), gk, dim3(ATT_THREADS), 0, s, p);
     }
-    if (dl_study_env("DL_ATTN_BWD_RING", 3) & 1) hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<T, HD, QT>), gq, dim3(ATT_THREADS), 0, s, p);
-    else hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD, QT, false>), gq, dim3(ATT_THREADS), 0, s, p);
-    if (dl_study_env("DL_ATTN_BWD_RING", 3) & 2) hipLaunchKernelGGL((attn_bwd_dkv_ring_kernel<T, HD, KT>), gk, dim3(ATT_THREADS), 0, s, p);
-    else hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, HD, KT, false>), gk, dim3(ATT_THREADS), 0, s, p);
-    return DL_OK;
+  } else {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD, QT, false>), gq, dim3(ATT_THREADS), 0, s, p);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, HD, KT, false>), gk, dim3(ATT_THREADS), 0, s, p);
   }
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD, QT, false>), gq, dim3(ATT_THREADS), 0, s, p);
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, HD, KT, false>), gk, dim3(ATT_THREADS), 0, s, p);
+  return DL_OK;
+}
+
+// the part of AttnP that dl_attn_fwd_args and dl_attn_bwd_args share (same field names), with the key-multiplicity checks
+template <typename Args>
+int fill_common(const char* who, const Args* a, AttnP& p) {
+  p.Q = (const char*)a->Q; p.K = (const char*)a->K; p.V = (const char*)a->V;
+  p.q_ps = a->q_ps; p.q_hs = a->q_hs; p.q_rs = a->q_rs; p.k_ps = a->k_ps; p.k_hs = a->k_hs; p.k_rs = a->k_rs;
+  p.v_ps = a->v_ps; p.v_hs = a->v_hs; p.v_rs = a->v_rs; p.o_ps = a->o_ps; p.o_hs = a->o_hs; p.o_rs = a->o_rs;
+  p.o_ss = a->o_ss;
+  p.P = a->n_problems; p.H = a->n_heads; p.S = a->n_segments; p.shift = a->partner_shift;
+  p.Lq = a->Lq; p.Lk = a->Lk; p.scale = a->scale; p.algo = a->algo;
+  DL_CHECK_ARG(a->key_tail_rows >= 0 && a->key_tail_rows <= a->Lk && (a->key_tail_rows == 0 || (a->key_tail_weight >= 1.f && a->scale > 0.f)),
+               DL_ERR_ARG, "%s: key_tail_rows in [0, Lk], key_tail_weight >= 1", who);
+  DL_CHECK_ARG(a->key_tail_rows == 0 || a->n_segments == 1, DL_ERR_UNSUPPORTED, "%s: key multiplicities with one segment only", who);
+  p.tail_start = a->Lk - a->key_tail_rows;
+  p.tail_bias = a->key_tail_rows ? logf(a->key_tail_weight) / a->scale : 0.f;
   return DL_OK;
 }
 
@@ -1415,18 +1430,9 @@ extern "C" int dl_attn_fwd(const dl_attn_fwd_args* a, dl_stream stream) {
   DL_CHECK_ARG(a->n_segments == 1 || (a->partner_shift >= 0 && a->partner_shift < a->n_problems),
                DL_ERR_ARG, "dl_attn_fwd: bad partner_shift");
   AttnP p = {};
-  p.Q = (const char*)a->Q; p.K = (const char*)a->K; p.V = (const char*)a->V; p.Out = (char*)a->O;
-  p.LSE = a->LSE; p.raw = a->raw_logits;
-  p.q_ps = a->q_ps; p.q_hs = a->q_hs; p.q_rs = a->q_rs; p.k_ps = a->k_ps; p.k_hs = a->k_hs; p.k_rs = a->k_rs;
-  p.v_ps = a->v_ps; p.v_hs = a->v_hs; p.v_rs = a->v_rs; p.o_ps = a->o_ps; p.o_hs = a->o_hs; p.o_rs = a->o_rs;
-  p.o_ss = a->o_ss;
-  p.P = a->n_problems; p.H = a->n_heads; p.S = a->n_segments; p.shift = a->partner_shift;
-  p.Lq = a->Lq; p.Lk = a->Lk; p.scale = a->scale; p.algo = a->algo;
-  DL_CHECK_ARG(a->key_tail_rows >= 0 && a->key_tail_rows <= a->Lk && (a->key_tail_rows == 0 || (a->key_tail_weight >= 1.f && a->scale > 0.f)),
-               DL_ERR_ARG, "dl_attn_fwd: key_tail_rows in [0, Lk], key_tail_weight >= 1");
-  DL_CHECK_ARG(a->key_tail_rows == 0 || a->n_segments == 1, DL_ERR_UNSUPPORTED, "dl_attn_fwd: key multiplicities with one segment only");
-  p.tail_start = a->Lk - a->key_tail_rows;
-  p.tail_bias = a->key_tail_rows ? logf(a->key_tail_weight) / a->scale : 0.f;
+  rc = fill_common("dl_attn_fwd", a, p);
+  if (rc != DL_OK) return rc;
+  p.Out = (char*)a->O; p.LSE = a->LSE; p.raw = a->raw_logits;
   dl_prof_before(1, s);
   if (a->dtype == DL_BF16) rc = a->head_dim == 64 ? launch_fwd<bf16_t, 64>(p, s) : launch_fwd<bf16_t, 128>(p, s);
   else rc = a->head_dim == 64 ? launch_fwd<float, 64>(p, s) : launch_fwd<float, 128>(p, s);
@@ -1451,22 +1457,13 @@ extern "C" int dl_attn_bwd(const dl_attn_bwd_args* a, dl_stream stream) {
   DL_CHECK_ARG(a->n_segments == 1 || (a->partner_shift >= 0 && a->partner_shift < a->n_problems),
                DL_ERR_ARG, "dl_attn_bwd: bad partner_shift");
   AttnP p = {};
-  p.Q = (const char*)a->Q; p.K = (const char*)a->K; p.V = (const char*)a->V; p.O = (const char*)a->O;
-  p.dO = (const char*)a->dO; p.LSE = const_cast<float*>(a->LSE); p.Delta = a->Delta;
+  rc = fill_common("dl_attn_bwd", a, p);
+  if (rc != DL_OK) return rc;
+  p.O = (const char*)a->O; p.dO = (const char*)a->dO; p.LSE = const_cast<float*>(a->LSE); p.Delta = a->Delta;
   p.dQ = (char*)a->dQ; p.dK = (char*)a->dK; p.dV = (char*)a->dV;
-  p.q_ps = a->q_ps; p.q_hs = a->q_hs; p.q_rs = a->q_rs; p.k_ps = a->k_ps; p.k_hs = a->k_hs; p.k_rs = a->k_rs;
-  p.v_ps = a->v_ps; p.v_hs = a->v_hs; p.v_rs = a->v_rs; p.o_ps = a->o_ps; p.o_hs = a->o_hs; p.o_rs = a->o_rs;
-  p.o_ss = a->o_ss;
   p.do_ps = a->do_ps; p.do_hs = a->do_hs; p.do_rs = a->do_rs; p.do_ss = a->do_ss;
   p.dq_ps = a->dq_ps; p.dq_hs = a->dq_hs; p.dq_rs = a->dq_rs; p.dk_ps = a->dk_ps; p.dk_hs = a->dk_hs;
   p.dk_rs = a->dk_rs; p.dv_ps = a->dv_ps; p.dv_hs = a->dv_hs; p.dv_rs = a->dv_rs;
-  p.P = a->n_problems; p.H = a->n_heads; p.S = a->n_segments; p.shift = a->partner_shift;
-  p.Lq = a->Lq; p.Lk = a->Lk; p.scale = a->scale; p.algo = a->algo;
-  DL_CHECK_ARG(a->key_tail_rows >= 0 && a->key_tail_rows <= a->Lk && (a->key_tail_rows == 0 || (a->key_tail_weight >= 1.f && a->scale > 0.f)),
-               DL_ERR_ARG, "dl_attn_bwd: key_tail_rows in [0, Lk], key_tail_weight >= 1");
-  DL_CHECK_ARG(a->key_tail_rows == 0 || a->n_segments == 1, DL_ERR_UNSUPPORTED, "dl_attn_bwd: key multiplicities with one segment only");
-  p.tail_start = a->Lk - a->key_tail_rows;
-  p.tail_bias = a->key_tail_rows ? logf(a->key_tail_weight) / a->scale : 0.f;
   dl_prof_before(2, s);
   if (a->dtype == DL_BF16) rc = a->head_dim == 64 ? launch_bwd<bf16_t, 64>(p, s) : launch_bwd<bf16_t, 128>(p, s);
   else rc = a->head_dim == 64 ? launch_bwd<float, 64>(p, s) : launch_bwd<float, 128>(p, s);

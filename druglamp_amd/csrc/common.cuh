@@ -32,22 +32,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 #define DL_LDS __attribute__((address_space(3)))
 
-// Study switches (tile forms that were measured and rejected, "skip the stores" timing decompositions ...) exist only
-// in a -DDL_STUDY build (`python -m druglamp_amd.build --study` -> libdruglamp_hip_study.so, used by tools/).  The
-// product library never reads the environment: dl_study_env() is the constant default there, so no stray variable
-// can change which kernel runs or make a kernel skip work.
-#ifdef DL_STUDY
-#include <stdlib.h>
-static inline int dl_study_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-#else
-static constexpr int dl_study_env(const char*, int dflt) { return dflt; }
-#endif
-// kernel-side view of a study bit field: the constant 0 in the product build, so the study branches are compiled out
-#ifdef DL_STUDY
-#define DL_DBG(p) ((p).dbg)
-#else
-#define DL_DBG(p) 0
-#endif
+// The library reads no environment: kernel selection depends on the call's arguments (shapes, dtypes, dl_gemm_args.algo, dl_attn_*_args.algo) only.
 
 extern "C" void dl_set_error(const char* fmt, ...);
 // profiling hooks (api.hip)
@@ -93,21 +78,6 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ float bf16lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
 __device__ __forceinline__ float bf16hi(uint32_t w) {
   return __builtin_bit_cast(float, w & 0xffff0000u);
-}
-
-// An fp32 quad rounded to the pipeline's storage type and back: the value a consumer of the STORED tensor would read.
-// STUDY BUILDS ONLY (round 6, tools/trickle_bench.py): gemm_trickle_kernel parks its finished tile in LDS as bf16, so its GELU /
-// gelu' / dropout / residual epilogues act on the rounded pre-activation; in a -DDL_STUDY build gemm_kernel and gemm_big_kernel
-// round at the same point so that the three kernels can be compared bit for bit.  The product library keeps the fp32 value
-// (one rounding per output): there dl_round_store is the identity.
-template <typename T> __device__ __forceinline__ f32x4 dl_round_store(f32x4 v) {
-#ifdef DL_STUDY
-  if constexpr (sizeof(T) == 2) {
-    const uint32_t a = pack_bf16x2(v[0], v[1]), b = pack_bf16x2(v[2], v[3]);
-    return f32x4{bf16lo(a), bf16hi(a), bf16lo(b), bf16hi(b)};
-  }
-#endif
-  return v;
 }
 
 // 4 consecutive elements of T <-> f32x4 (global memory, vector access)
@@ -246,18 +216,12 @@ __device__ __forceinline__ float group4_max(float v) {
 }
 
 // Output stores of the GEMM epilogues carry the `nt` (streaming) policy: 65536x2048x512 plain 189 -> 153 us, 65536x1024x256
-// 52 -> 49, 65536x512x2048 131 -> 119 (tools/epi_bench.py with DL_NT_MODE; sc1 / sc0 sc1 write-through forms are slower
-// than plain).  The store phases of the persistent grid arrive as 33 MB bursts (one 128 KB tile per CU); with the default
-// policy the lines are allocated in the XCD's 4 MB L2 and evict the operand panels the next main loops re-read.
-// mode 1 (product): the compiler's non-temporal store; study modes: 2 = inline assembly with nt (within 1-3 % of the builtin;
-// needs s_nop — the hazard recogniser cannot see into the asm and a VALU write of the data registers directly behind a
-// store of more than 8 bytes corrupts single outputs), 3 = inline assembly with the default policy (as slow as the plain
-// store: it is the policy, not the compiler's bookkeeping of the store)
-__device__ __forceinline__ void store16_nt(void* dst, u32x4 v, int mode = 1) {
-#ifdef DL_STUDY
-  if (mode == 2) { asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 2" ::"v"(dst), "v"(v) : "memory"); return; }
-  if (mode == 3) { asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 2" ::"v"(dst), "v"(v) : "memory"); return; }
-#endif
+// 52 -> 49, 65536x512x2048 131 -> 119 (tools/epi_bench.py; sc1 / sc0 sc1 write-through forms are slower than plain).
+// The store phases of the persistent grid arrive as 33 MB bursts (one 128 KB tile per CU); with the default policy the
+// lines are allocated in the XCD's 4 MB L2 and evict the operand panels the next main loops re-read.  The store is the
+// compiler's non-temporal store (inline assembly with nt was within 1-3 % of it; inline assembly with the default policy
+// as slow as the plain store: it is the policy, not the compiler's bookkeeping of the store).
+__device__ __forceinline__ void store16_nt(void* dst, u32x4 v) {
   __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst));
 }
 __device__ __forceinline__ u32x4 load16_nt(const void* src) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src)); }

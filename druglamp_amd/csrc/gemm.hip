@@ -48,7 +48,6 @@ struct GemmP {
   int accumulate;
   float* slabs;   // split mode: [splits][M][N] f32
   float* cs_slabs; // split mode, optional: [splits][M] partial column sums of the K-slow X operand
-  int dbg;
   int nt_c = 0, nt_pre = 0, nt_small = 0, nt_ext = 0;   // large-tile kernels: streaming (`nt`) policy for the output / pre-activation stores
   // paired launch (gemm_kernel only): byte offsets from problem 0's pointers to problem 1's, and the seed difference
   int nprob = 1;
@@ -224,7 +223,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmP p0) {
   u32x4 rx[TW], rw[TW];
   uint32_t it = blockIdx.x;
   if (it >= ntiles) return;
-  if ((DL_DBG(p) & 4) && (blockIdx.x >= gridDim.x / 2)) { for (int z = 0; z < (DL_DBG(p) >> 4); ++z) __builtin_amdgcn_s_sleep(127); }
   int split, m0, n0, kbeg, kend;
   locate(it, split, m0, n0, kbeg, kend);
   if constexpr (!XD) load_tile<T, XS, TW>(Xb, p.ldx, m0, p.M, kbeg, kend, rx);
@@ -256,7 +254,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmP p0) {
       char* cur = smem + (kt & 1) * 2 * TB;
       char* nxt = smem + ((kt + 1) & 1) * 2 * TB;
       const bool more = (kt + 1 < nk);
-      if (more && !(DL_DBG(p) & 2)) {
+      if (more) {
         if constexpr (XD) dma_tile<T, XS, TW>(Xb, p.ldx, m0, p.M, kbeg + (kt + 1) * BKE, nxt);
         else load_tile<T, XS, TW>(Xb, p.ldx, m0, p.M, kbeg + (kt + 1) * BKE, kend, rx);
         if constexpr (WD) dma_tile<T, WS, TW>(Wb, p.ldw, n0, p.N, kbeg + (kt + 1) * BKE, nxt + TB);
@@ -345,7 +343,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmP p0) {
     const int row = c / (BN / 8), cc = (c % (BN / 8)) * 8;
     const int m = cm0 + row, n = cn0 + cc;
     if (m >= p.M || n >= p.N) continue;
-    if ((DL_DBG(p) & 1)) continue;
     if constexpr (SIMPLE && !SPLIT) {
       // bias-only epilogue, N % 8 == 0: straight LDS -> (bias) -> convert -> one 16-byte store
       f32x4 a0 = *reinterpret_cast<const f32x4*>(smem + row * EP + cc * 4);
@@ -354,7 +351,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmP p0) {
       TO* dst = reinterpret_cast<TO*>(p.C) + (int64_t)m * p.ldc + n;
       if constexpr (sizeof(TO) == 2) {
         u32x4 o = {pack_bf16x2(a0[0], a0[1]), pack_bf16x2(a0[2], a0[3]), pack_bf16x2(a1[0], a1[1]), pack_bf16x2(a1[2], a1[3])};
-        if (p.nt_c && p.nt_small) store16_nt(dst, o, p.nt_c);
+        if (p.nt_c && p.nt_small) store16_nt(dst, o);
         else *reinterpret_cast<u32x4*>(dst) = o;
       } else {
         *reinterpret_cast<f32x4*>(dst) = a0;
@@ -366,9 +363,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmP p0) {
       f32x4 a0 = *reinterpret_cast<const f32x4*>(smem + row * EP + cc * 4);
       f32x4 a1 = *reinterpret_cast<const f32x4*>(smem + row * EP + cc * 4 + 16);
       if (EPI != 4) { a0 += hb0; a1 += hb1; }
-      if constexpr ((EPI == 2 || EPI == 3 || EPI == 4) && sizeof(T) == 2 && sizeof(TO) == 2) {       // (common.cuh: as the large-tile kernels)
-        a0 = dl_round_store<T>(a0); a1 = dl_round_store<T>(a1);
-      }
       if constexpr (EPI == 2) {
         T* pd = reinterpret_cast<T*>(p.pre_out) + (int64_t)m * p.ldp + n;
         store4<T>(pd, a0); store4<T>(pd + 4, a1);
@@ -392,7 +386,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmP p0) {
       TO* dst = reinterpret_cast<TO*>(p.C) + (int64_t)m * p.ldc + n;
       if constexpr (sizeof(TO) == 2) {
         u32x4 o = {pack_bf16x2(a0[0], a0[1]), pack_bf16x2(a0[2], a0[3]), pack_bf16x2(a1[0], a1[1]), pack_bf16x2(a1[2], a1[3])};
-        if (p.nt_c && p.nt_small) store16_nt(dst, o, p.nt_c);
+        if (p.nt_c && p.nt_small) store16_nt(dst, o);
         else *reinterpret_cast<u32x4*>(dst) = o;
       } else {
         *reinterpret_cast<f32x4*>(dst) = a0;
@@ -507,9 +501,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmP p0) {
 }
 
 #include "gemm_big.cuh"
-#ifdef DL_STUDY          // (round 6 study kernel: measured and NOT adopted — tools/trickle_bench.py, profiles/r6_trickle_study.txt)
-#include "gemm_trickle.cuh"
-#endif
 
 // out[idx] (+)= sum_z slabs[z][idx]
 template <typename TO>
@@ -561,7 +552,7 @@ int pick_tw(const dl_gemm_args* a) {
 int auto_split(int64_t M, int64_t N, int64_t K, int bke, int bt) {
   const int64_t tiles = ((M + bt - 1) / bt) * ((N + bt - 1) / bt);
   if (tiles >= 192) return 1;
-  const int round_wgs = dl_study_env("DL_SPLIT_ROUND", 512), max_sp = dl_study_env("DL_SPLIT_MAX", 256);
+  constexpr int round_wgs = 512, max_sp = 256;
   int64_t want = round_wgs / tiles;        // floor: tiles * splits must fit ONE round of 512 resident workgroups (a
                                            // 516-workgroup plan ran 4 of them alone in a second round: 768x256, +25 %)
   if (want < 1) want = 1;
@@ -621,130 +612,29 @@ bool big_eligible(const dl_gemm_args* a, const GemmP& p, int sp) {
   const int64_t tiles = ((a->M + 255) / 256) * ((a->N + 255) / 256);
   return tiles >= 192;
 }
-int big_cfg() { return dl_study_env("DL_GEMM_BIGCFG", 0); }
-#ifdef DL_STUDY
-// Trickle form (gemm_trickle.cuh; STUDY LIBRARY ONLY, opt-in through DL_GEMM_TRICKLE=1): 256x128 tiles whose epilogue drains from
-// LDS inside the next tile's main loop.  Returns the pieces per k-step (0 = not eligible).  Needs whole tiles (M % 256, N % 128),
-// K = 256 or a multiple of 512 (the piece schedule), static tile order, one of the epilogues {plain / bias, bias + GELU +
-// pre-activation, bias + residual, gelu'}.
-int trickle_ppk(const dl_gemm_args* a, const GemmP& p, int sp) {
-  if (dl_study_env("DL_GEMM_TRICKLE", 0) == 0) return 0;
-  if (!big_eligible(a, p, sp) || p.tickets) return 0;
-  const int epi = pick_epi(p, false);
-  if (!(epi == 0 || epi == 2 || epi == 3 || epi == 4)) return 0;
-  if (a->N % 128 != 0 || a->N / 128 > 256 || a->M % 256 != 0) return 0;
-  const int64_t kmax = dl_study_env("DL_GEMM_TRICKLE_MAXK", 2048);
-  if (a->K > kmax) return 0;
-  if (a->K == 256) return 2;
-  return a->K % 512 == 0 ? 1 : 0;
-}
-void launch_trickle(const GemmP& p, hipStream_t s, int ppk) {
-  const uint32_t ntiles = (uint32_t)p.mt * p.nt;
-  uint32_t nblocks = (256u / (uint32_t)p.nt) * (uint32_t)p.nt;            // a workgroup keeps its column tile: bias / columns fixed per launch
-  if (nblocks > ntiles) nblocks = ntiles;
-#define DL_TRK(E)                                                                                            \
-  do {                                                                                                       \
-    if (ppk == 2) hipLaunchKernelGGL((gemm_trickle_kernel<E, 2>), dim3(nblocks), dim3(512), 0, s, p);      \
-    else hipLaunchKernelGGL((gemm_trickle_kernel<E, 1>), dim3(nblocks), dim3(512), 0, s, p);               \
-  } while (0)
-  switch (pick_epi(p, false)) {
-    case 0: DL_TRK(0); break;
-    case 2: DL_TRK(2); break;
-    case 3: DL_TRK(3); break;
-    default: DL_TRK(4); break;
-  }
-#undef DL_TRK
-}
-#else
-static inline int trickle_ppk(const dl_gemm_args*, const GemmP&, int) { return 0; }
-static inline void launch_trickle(const GemmP&, hipStream_t, int) {}
-#endif
 // Few-tile ("latency") form of the same kernel: a 128x128 tile per 4-wave workgroup with a DEEP stage ring.  When the
 // whole output is at most a round or two of tiles (strong-scaling batches: M = 8192 ... 32768 rows) every workgroup walks
 // its k-steps alone on its CU, and gemm_kernel's two-buffer ring pays one full memory round trip per k-step; three
-// steps in flight divide that by three.  Returns the variant (0 = not eligible).
-int lat_cfg() { return dl_study_env("DL_GEMM_LATCFG", 1); }
-int lat_eligible(const dl_gemm_args* a, const GemmP& p, int sp) {
-  const int cfg = lat_cfg();
-  if (cfg == 0 || a->algo == DL_GEMM_ALGO_TILE128) return 0;
-  if (sp > 1 || a->in_dtype != DL_BF16 || a->out_dtype != DL_BF16 || a->x_kslow || a->w_kslow) return 0;
-  if (pick_epi(p, false) == 1) return 0;
+// steps in flight divide that by three.
+constexpr int LAT_MIN_K = 512;       // >= 8 k-steps
+constexpr int LAT_MAX_TILES = 256;   // one round of one workgroup per CU
+bool lat_eligible(const dl_gemm_args* a, const GemmP& p, int sp) {
+  if (a->algo == DL_GEMM_ALGO_TILE128) return false;
+  if (sp > 1 || a->in_dtype != DL_BF16 || a->out_dtype != DL_BF16 || a->x_kslow || a->w_kslow) return false;
+  if (pick_epi(p, false) == 1) return false;
   // measured (tools/latency_gemm_bench.py, M = 8192 / 16384 / 32768): 10-25 % faster than the two-buffer ring when the
   // tiles fit ONE round of one-workgroup-per-CU and there are >= 8 k-steps; with two rounds, or at K = 256, the
   // two-workgroups-per-CU ring of gemm_kernel wins
-  if (a->K % 64 != 0 || a->K < dl_study_env("DL_GEMM_LATMINK", 512) || a->N < 128) return 0;
+  if (a->K % 64 != 0 || a->K < LAT_MIN_K || a->N < 128) return false;
   const int64_t tiles = ((a->M + 127) / 128) * ((a->N + 127) / 128);
-  if (tiles > dl_study_env("DL_GEMM_LATMAX", 256)) return 0;
-  return cfg;
+  return tiles <= LAT_MAX_TILES;
 }
-void launch_lat(const GemmP& p, hipStream_t s, int cfg) {
+// one launch of a gemm_big_kernel tile form with the call's specialised epilogue
+template <int XF, int WM, int WN, int RB, int NS>
+void launch_big_form(const GemmP& p, hipStream_t s, uint32_t max_wgs, uint32_t threads) {
   const uint32_t ntiles = (uint32_t)p.mt * p.nt;
-#define DL_LAT_SW(XF_, RB_, NS_, WGS_)                                                                              \
-  {                                                                                                                  \
-    const uint32_t nblocks = ntiles < (WGS_) ? ntiles : (WGS_);                                                      \
-    switch (pick_epi(p, false)) {                                                                                    \
-      case 0: hipLaunchKernelGGL((gemm_big_kernel<XF_, 2, 2, RB_, NS_, 0>), dim3(nblocks), dim3(256), 0, s, p); break; \
-      case 2: hipLaunchKernelGGL((gemm_big_kernel<XF_, 2, 2, RB_, NS_, 2>), dim3(nblocks), dim3(256), 0, s, p); break; \
-      case 3: hipLaunchKernelGGL((gemm_big_kernel<XF_, 2, 2, RB_, NS_, 3>), dim3(nblocks), dim3(256), 0, s, p); break; \
-      case 4: hipLaunchKernelGGL((gemm_big_kernel<XF_, 2, 2, RB_, NS_, 4>), dim3(nblocks), dim3(256), 0, s, p); break; \
-      default: hipLaunchKernelGGL((gemm_big_kernel<XF_, 2, 2, RB_, NS_, 5>), dim3(nblocks), dim3(256), 0, s, p); break; \
-    }                                                                                                                \
-  }
-#ifdef DL_STUDY
-  if (cfg == 2) { DL_LAT_SW(4, 128, 3, 256u); return; }       // 96 KB ring, one workgroup per CU
-  if (cfg == 3) { DL_LAT_SW(4, 64, 4, 512u); return; }        // 64-byte rows: 64 KB ring, two workgroups per CU
-#endif
-  DL_LAT_SW(4, 128, 4, 256u);                                 // 128 KB ring, one workgroup per CU, three steps in flight
-#undef DL_LAT_SW
-}
-void launch_big(const GemmP& p, hipStream_t s) {
-  const uint32_t ntiles = (uint32_t)p.mt * p.nt;
-#ifdef DL_STUDY        // (the three rejected tile forms are instantiated in the study library only: 15 kernels the product never launches)
-  const int cfg = big_cfg();
-  // tile studies (DL_GEMM_BIGCFG): 1 = 256x128 tiles, 64-byte rows, 3 stages, two 4-wave workgroups per CU;
-  // 2 = 256x256 tiles, 64-byte rows, 4 stages
-  if (cfg == 1) {
-    const uint32_t nblocks = ntiles < 512u ? ntiles : 512u;
-#define DL_BIG(E) hipLaunchKernelGGL((gemm_big_kernel<8, 2, 2, 64, 3, E>), dim3(nblocks), dim3(256), 0, s, p)
-    switch (pick_epi(p, false)) {
-      case 0: DL_BIG(0); break;
-      case 2: DL_BIG(2); break;
-      case 3: DL_BIG(3); break;
-      case 4: DL_BIG(4); break;
-      default: DL_BIG(5); break;
-    }
-#undef DL_BIG
-    return;
-  }
-#endif
-  const uint32_t nblocks = ntiles < 256u ? ntiles : 256u;       // one 128 KB workgroup per CU
-#ifdef DL_STUDY
-  if (cfg == 3) {               // 16 waves of 64x64 (four per SIMD) on the same 256x256 tile and stage ring
-#define DL_BIG(E) hipLaunchKernelGGL((gemm_big_kernel<4, 4, 4, 128, 2, E>), dim3(nblocks), dim3(1024), 0, s, p)
-    switch (pick_epi(p, false)) {
-      case 0: DL_BIG(0); break;
-      case 2: DL_BIG(2); break;
-      case 3: DL_BIG(3); break;
-      case 4: DL_BIG(4); break;
-      default: DL_BIG(5); break;
-    }
-#undef DL_BIG
-    return;
-  }
-  if (cfg == 2) {
-#define DL_BIG(E) hipLaunchKernelGGL((gemm_big_kernel<8, 2, 4, 64, 4, E>), dim3(nblocks), dim3(512), 0, s, p)
-    switch (pick_epi(p, false)) {
-      case 0: DL_BIG(0); break;
-      case 2: DL_BIG(2); break;
-      case 3: DL_BIG(3); break;
-      case 4: DL_BIG(4); break;
-      default: DL_BIG(5); break;
-    }
-#undef DL_BIG
-    return;
-  }
-#endif
-#define DL_BIG(E) hipLaunchKernelGGL((gemm_big_kernel<8, 2, 4, 128, 2, E>), dim3(nblocks), dim3(512), 0, s, p)
+  const uint32_t nblocks = ntiles < max_wgs ? ntiles : max_wgs;
+#define DL_BIG(E) hipLaunchKernelGGL((gemm_big_kernel<XF, WM, WN, RB, NS, E>), dim3(nblocks), dim3(threads), 0, s, p)
   switch (pick_epi(p, false)) {
     case 0: DL_BIG(0); break;
     case 2: DL_BIG(2); break;
@@ -754,6 +644,8 @@ void launch_big(const GemmP& p, hipStream_t s) {
   }
 #undef DL_BIG
 }
+void launch_lat(const GemmP& p, hipStream_t s) { launch_big_form<4, 2, 2, 128, 4>(p, s, 256u, 256u); }   // 128x128 tiles, 128 KB ring, three steps in flight
+void launch_big(const GemmP& p, hipStream_t s) { launch_big_form<8, 2, 4, 128, 2>(p, s, 256u, 512u); }   // 256x256 tiles, one 128 KB workgroup per CU
 
 // Large-tile weight-gradient path (gemm_big_tt2_kernel): bf16 operands, both K-slow, plain fp32 output through
 // split-K slabs.  Returns the slab count (0 = not eligible); *bm_out is the tile height (256 or 128; 256 columns).
@@ -764,7 +656,7 @@ int big_tt_plan(const dl_gemm_args* a, int* bm_out) {
   if (!plain || a->M % 8 != 0 || a->N % 8 != 0 || a->N < 192 || a->M < 96 || a->K < 4096) return 0;
   // One round of 256 workgroups writes 256 fp32 tiles of slabs whatever the problem, so a tile only pays when the
   // operand stream dwarfs that.  256x256 tiles from 640K outputs (2048x512, 1536x512); below that 128x256 tiles
-  // (same slab bytes as the 128-tile kernel's 512-workgroup plan) where tools/tt_study.py measured a win:
+  // (same slab bytes as the 128-tile kernel's 512-workgroup plan) where profiles/r3_tt_study.txt records a win:
   // 1024x256, 256x1024, 768x256, 512x512, 256x648 at K = 65536, 256x392 at K = 131072 (5-17 %), the
   // 128 x {768, 1152} x 591864 conv gradients (20-25 %); NOT 256x512 / 256x256 at K = 65536 or 128x384x591870.
   const bool big = a->M > 128 && a->M * a->N >= 640 * 1024;
@@ -790,15 +682,6 @@ void launch_big_tt2(const GemmP& p, hipStream_t s, uint32_t nblocks) {
 void launch_big_tt(const GemmP& p, hipStream_t s, int bm) {
   const uint32_t ntiles = (uint32_t)p.mt * p.nt * p.splits;
   const uint32_t nblocks = ntiles < 256u ? ntiles : 256u;
-#ifdef DL_STUDY
-  // rejected forms (tools/tt_study.py): two 64-row stages (one step in flight), the L2 prefetch, five 32-row stages
-  switch (dl_study_env("DL_GEMM_TTCFG", 0)) {
-    case 1: if (bm == 256) launch_big_tt2<8, 64, 2, false>(p, s, nblocks); else launch_big_tt2<4, 64, 2, false>(p, s, nblocks); return;
-    case 2: if (bm == 256) launch_big_tt2<8, 64, 2, true>(p, s, nblocks); else launch_big_tt2<4, 64, 2, true>(p, s, nblocks); return;
-    case 4: if (bm == 256) launch_big_tt2<8, 32, 4, true>(p, s, nblocks); else launch_big_tt2<4, 64, 3, true>(p, s, nblocks); return;
-    default: break;
-  }
-#endif
   // 256x256: four 32-row stages (three steps in flight); 128x256: three 64-row stages
   if (bm == 256) launch_big_tt2<8, 32, 4, false>(p, s, nblocks); else launch_big_tt2<4, 64, 3, false>(p, s, nblocks);
 }
@@ -842,7 +725,7 @@ template <typename T, typename TO, bool SPLIT>
 int dispatch_layout(const dl_gemm_args* a, const GemmP& p, hipStream_t s, int tw) {
   // LDS-DMA staging needs whole K steps per split and at least one K-contiguous operand
   const int bke = BKB / (int)sizeof(T);
-  const bool dma = (a->K % bke == 0) && (p.k_per_split % bke == 0) && !(DL_DBG(p) & 8);
+  const bool dma = (a->K % bke == 0) && (p.k_per_split % bke == 0);
   if (!a->x_kslow && !a->w_kslow) { if (dma) launch<T, TO, false, false, SPLIT, true>(p, s, tw); else launch<T, TO, false, false, SPLIT, false>(p, s, tw); }
   else if (!a->x_kslow && a->w_kslow) { if (dma) launch<T, TO, false, true, SPLIT, true>(p, s, tw); else launch<T, TO, false, true, SPLIT, false>(p, s, tw); }
   else if (a->x_kslow && a->w_kslow) { if (dma) launch<T, TO, true, true, SPLIT, true>(p, s, tw); else launch<T, TO, true, true, SPLIT, false>(p, s, tw); }
@@ -933,7 +816,6 @@ int gemm_run(const dl_gemm_args* a, const dl_gemm_args* b, dl_stream stream) {
   else DL_CHECK_ARG(a->M % epc == 0, DL_ERR_ALIGN, "dl_gemm: M %% %d != 0 for k-slow X", epc);
   if (!a->w_kslow) DL_CHECK_ARG(a->K % epc == 0, DL_ERR_ALIGN, "dl_gemm: K %% %d != 0", epc);
   else DL_CHECK_ARG(a->N % epc == 0, DL_ERR_ALIGN, "dl_gemm: N %% %d != 0 for k-slow W", epc);
-  const int oes = (int)dl_dtype_size(a->out_dtype);
   if (a->N % 8 == 0) {
     DL_CHECK_ARG(a->ldc % 8 == 0 && ((uintptr_t)a->C % 16) == 0, DL_ERR_ALIGN,
                  "dl_gemm: C / ldc not aligned for 16-byte stores (N %% 8 == 0 path)");
@@ -991,14 +873,8 @@ int gemm_run(const dl_gemm_args* a, const dl_gemm_args* b, dl_stream stream) {
   p.accumulate = a->accumulate;
   p.slabs = (float*)a->workspace;
   p.cs_slabs = a->x_colsum ? (float*)a->workspace + (size_t)sp * a->M * a->N : nullptr;
-  p.dbg = dl_study_env("DL_GEMM_DBG", 0);     // 0 in the product build (kernels compile the study branches out)
-  {
-    const double out_mb = (double)a->M * (double)a->N * oes / 1e6;
-    p.nt_c = out_mb >= (double)dl_study_env("DL_NT_MIN_MB", 0) ? dl_study_env("DL_NT_MODE", 1) : 0;
-    p.nt_pre = dl_study_env("DL_NT_PRE", 1) ? dl_study_env("DL_NT_MODE", 1) : 0;
-    p.nt_small = dl_study_env("DL_NT_SMALL", 1);
-    p.nt_ext = dl_study_env("DL_NT_EXT", 0);       // residual / saved pre-activation reads of the large-tile epilogues
-  }
+  p.nt_c = 1; p.nt_pre = 1; p.nt_small = 1;
+  p.nt_ext = 0;       // residual / saved pre-activation reads of the large-tile epilogues
 
   if (b) {
     // a pair shares a launch only on the gemm_kernel path without split-K; anything else runs as two launches
@@ -1021,15 +897,12 @@ int gemm_run(const dl_gemm_args* a, const dl_gemm_args* b, dl_stream stream) {
     const int64_t ksteps = (a->K + 63) / 64;
     p.k_per_split = (int)(((ksteps + sp - 1) / sp) * 64);
     launch_big_tt(p, s, tt_bm);
-  } else if (const int ppk = trickle_ppk(a, p, sp)) {
-    p.mt = (int)((a->M + 255) / 256); p.nt = (int)(a->N / 128);
-    launch_trickle(p, s, ppk);
   } else if (big_eligible(a, p, sp)) {
-    p.mt = (int)((a->M + 255) / 256); p.nt = (int)((a->N + (big_cfg() == 1 ? 127 : 255)) / (big_cfg() == 1 ? 128 : 256));
+    p.mt = (int)((a->M + 255) / 256); p.nt = (int)((a->N + 255) / 256);
     launch_big(p, s);
-  } else if (const int lat = b ? 0 : lat_eligible(a, p, sp)) {
+  } else if (!b && lat_eligible(a, p, sp)) {
     p.mt = (int)((a->M + 127) / 128); p.nt = (int)((a->N + 127) / 128);
-    launch_lat(p, s, lat);
+    launch_lat(p, s);
   } else if (a->in_dtype == DL_BF16) {
     if (slab_path) rc = dispatch_layout<bf16_t, float, true>(a, p, s, tw);
     else if (a->out_dtype == DL_F32) rc = dispatch_layout<bf16_t, float, false>(a, p, s, tw);
@@ -1100,8 +973,8 @@ int group_plan(const dl_gemm_args* args, int n, int* splits, int* bm_out) {
   // least 16384 rows: half the W-operand re-reads of the 128-row tile; elsewhere the 128-row tile's parallelism wins.
   // Batch 256 with every block grouped: 15.80 ms with 128-row tiles only, 15.52 with this rule (15.60 with the large
   // products left on their own launches); batch 128: 8.87 -> 8.77; batch 64: 5.79 -> 5.75; batch 32: no difference
-  const int want = dl_study_env("DL_GROUP_BM", 0);       // study: 128 / 256 force a tile height
-  const int bm = want == 128 ? 128 : (2 * big_mn >= all_mn && min_m >= 256 && min_steps >= dl_study_env("DL_GROUP_BM_MINSTEPS", 256)) ? 256 : 128;
+  constexpr int64_t bm256_min_steps = 256;     // 16384 rows of 64-row k-steps
+  const int bm = (2 * big_mn >= all_mn && min_m >= 256 && min_steps >= bm256_min_steps) ? 256 : 128;
   int64_t tiles = 0;
   for (int i = 0; i < n; ++i) tiles += ((args[i].M + bm - 1) / bm) * ((args[i].N + 255) / 256);
   int64_t sp = 256 / tiles;
@@ -1130,7 +1003,7 @@ extern "C" int dl_gemm_group(const dl_gemm_args* args, int32_t n, dl_stream stre
   int sp[DL_GROUP_MAX], bm = 128;
   DL_CHECK_ARG(group_plan(args, n, sp, &bm), DL_ERR_UNSUPPORTED, "dl_gemm_group: the group is not eligible (see dl_gemm_group_plan)");
   GemmGroupP gp;
-  gp.n = n; gp.dbg = dl_study_env("DL_GEMM_DBG", 0);
+  gp.n = n;
   uint32_t end = 0;
   double flops = 0.0, bytes = 0.0;
   for (int i = 0; i < n; ++i) {

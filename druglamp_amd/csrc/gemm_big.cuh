@@ -25,17 +25,16 @@
 // offset per tensor that is the same for every piece and tile (lo_c / lo_p: output, pre-activation copy), and the dropout group
 // index is a scalar plus the lane's constant.  Rounds 1-5 multiplied row * ld (and row * N for the dropout key) per piece in
 // 64-bit vector arithmetic: five quarter-rate integer multiplies = 4 of the ~27 VALU slots per output element of the GELU +
-// dropout epilogue, which is VALU-bound (tools/trickle_parts.py).
+// dropout epilogue, which is VALU-bound (profiles/r6_trickle_study.txt).
 template <int EPI>
 __device__ __forceinline__ void big_epilogue8(const GemmP& p, uint64_t seed_eff, int row_s, int n0_s, uint32_t lo_c, uint32_t lo_p, uint32_t lo_g,
                                               f32x4 a0, f32x4 a1, f32x4 b0, f32x4 b1, u32x4 ext) {
   typedef bf16_t T;
   if constexpr (EPI != 4) { a0 += b0; a1 += b1; }
-  if constexpr (EPI == 2 || EPI == 3 || EPI == 4) { a0 = dl_round_store<T>(a0); a1 = dl_round_store<T>(a1); }   // (study builds only: common.cuh)
   if constexpr (EPI == 2) {
     char* pd = p.pre_out + ((int64_t)row_s * p.ldp + n0_s) * 2 + lo_p;
     u32x4 o = {pack_bf16x2(a0[0], a0[1]), pack_bf16x2(a0[2], a0[3]), pack_bf16x2(a1[0], a1[1]), pack_bf16x2(a1[2], a1[3])};
-    if (p.nt_pre) store16_nt(pd, o, p.nt_pre);
+    if (p.nt_pre) store16_nt(pd, o);
     else *reinterpret_cast<u32x4*>(pd) = o;
     a0 = gelu4<T>(a0); a1 = gelu4<T>(a1);
   } else if constexpr (EPI == 5) {
@@ -56,7 +55,7 @@ __device__ __forceinline__ void big_epilogue8(const GemmP& p, uint64_t seed_eff,
   }
   u32x4 o = {pack_bf16x2(a0[0], a0[1]), pack_bf16x2(a0[2], a0[3]), pack_bf16x2(a1[0], a1[1]), pack_bf16x2(a1[2], a1[3])};
   char* dstp = p.C + ((int64_t)row_s * p.ldc + n0_s) * 2 + lo_c;
-  if (p.nt_c) store16_nt(dstp, o, p.nt_c);
+  if (p.nt_c) store16_nt(dstp, o);
   else *reinterpret_cast<u32x4*>(dstp) = o;
 }
 
@@ -223,12 +222,8 @@ void gemm_big_kernel(const GemmP p) {
     // dynamic hand-out: the ticket of the NEXT tile is drawn while this tile's main loop runs (its latency hides behind
     // the k-steps; every k-step has a workgroup barrier, so the word is visible to all waves long before it is read)
     if (dyn && tid == 0) *ticket_s = G + (uint32_t)__hip_atomic_fetch_add(p.tickets, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (DL_DBG(p) & 2) {                   // timing study: no operand feed after the prologue (results are garbage)
-      for (int kt = 0; kt < nk; ++kt) kstep(std::false_type{}, kt);
-    } else {
-      for (int kt = 0; kt + D < nk; ++kt) kstep(std::true_type{}, kt);
-      for (int kt = max(nk - D, 0); kt < nk; ++kt) kstep(std::false_type{}, kt);
-    }
+    for (int kt = 0; kt + D < nk; ++kt) kstep(std::true_type{}, kt);
+    for (int kt = max(nk - D, 0); kt < nk; ++kt) kstep(std::false_type{}, kt);
 
     // ---- tile end: request the next tile's first stages, then the epilogue --------------------
     const int cm0 = m0, cn0 = n0;
@@ -295,7 +290,7 @@ void gemm_big_kernel(const GemmP p) {
           const f32x4 a0 = __builtin_bit_cast(f32x4, lds_read16(st, r * 256 + (((2 * c8) ^ r) << 4)));
           const f32x4 a1 = __builtin_bit_cast(f32x4, lds_read16(st, r * 256 + (((2 * c8 + 1) ^ r) << 4)));
           const int row_s = row0_s + ro_of(item);
-          if (row_s + lr < p.M && n_ok && !(DL_DBG(p) & 1))
+          if (row_s + lr < p.M && n_ok)
             big_epilogue8<EPI>(p, seed_eff, row_s, n0_s, lo_c, lo_p, lo_g, a0, a1, b0, b1, ext[item]);
         }
         wave_sync();
@@ -326,7 +321,7 @@ __device__ __attribute__((aligned(16))) const uint32_t dl_zero_page[4] = {0u, 0u
 
 // ---------------------------------------------------------------------------------------------------------
 // Round 3: the weight-gradient tile with a deep feed (round 2's gemm_big_tt_kernel: two 64-row stages, DMA through the
-// builtin).  Measured on 2048x512x65536 (tools/tt_study.py): the builtin's DMA made the compiler drain every transposing
+// builtin).  Measured on 2048x512x65536 (profiles/r3_tt_study.txt): the builtin's DMA made the compiler drain every transposing
 // fragment read (compute-only 218 -> 141 us with the inline-assembly form), and with ONE step in flight the loop waits
 // for first-touch HBM data every step (every k-row of a weight gradient is read once): 32-row steps x 4 stages =
 // three steps in flight, 242 -> 164 us.
@@ -357,7 +352,7 @@ struct GroupProb {
   int M, N, K, k_per_split, mt, nt;
   uint32_t end; int pad;
 };
-struct GemmGroupP { int n; int dbg; GroupProb q[DL_GROUP_MAX]; };
+struct GemmGroupP { int n; GroupProb q[DL_GROUP_MAX]; };
 
 template <int XF, int NWM, int NWN, bool CS, int KS, int NSTAGE, bool PF, bool GROUP = false>
 __global__ __launch_bounds__(64 * NWM * NWN, 2) void gemm_big_tt2_kernel(const std::conditional_t<GROUP, GemmGroupP, GemmP> p) {
@@ -566,15 +561,11 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void gemm_big_tt2_kernel(const s
     };
     auto kloop = [&](auto with_cs) __attribute__((always_inline)) {
       typedef std::integral_constant<int, 0> F0; typedef std::integral_constant<int, 1> F1; typedef std::integral_constant<int, 2> F2;
-      if (DL_DBG(p) & 2) {
-        for (int kt = 0; kt < nk; ++kt) kstep(with_cs, F0{}, kt);
-      } else {
-        const int nwhole = len / KS;                        // steps [0, nwhole) are whole; step nwhole (if any) is partial
-        int kt = 0;
-        for (; kt + D < nwhole; ++kt) kstep(with_cs, F1{}, kt);
-        if (kt + D < nk) { kstep(with_cs, F2{}, kt); ++kt; }
-        for (; kt < nk; ++kt) kstep(with_cs, F0{}, kt);
-      }
+      const int nwhole = len / KS;                        // steps [0, nwhole) are whole; step nwhole (if any) is partial
+      int kt = 0;
+      for (; kt + D < nwhole; ++kt) kstep(with_cs, F1{}, kt);
+      if (kt + D < nk) { kstep(with_cs, F2{}, kt); ++kt; }
+      for (; kt < nk; ++kt) kstep(with_cs, F0{}, kt);
     };
     if constexpr (CS) {
       if (do_cs) kloop(std::true_type{}); else kloop(std::false_type{});
@@ -613,7 +604,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void gemm_big_tt2_kernel(const s
         const u32x4 a0 = lds_read16(st, r * 256 + (((2 * c8) ^ r) << 4));
         const u32x4 a1 = lds_read16(st, r * 256 + (((2 * c8 + 1) ^ r) << 4));
         const int m = cm0 + wm * 16 * XF + i * 16 + r, n = cn0 + wn * 16 * WF + c8 * 8;
-        if (m < eM && n < eN && !(DL_DBG(p) & 1)) {
+        if (m < eM && n < eN) {
           float* dst = eslabs + ((int64_t)csplit * eM + m) * eN + n;
           store16_fam<8>(dst, a0);
           store16_fam<8>(dst + 4, a1);

@@ -30,6 +30,17 @@ def test_c_abi_exports_every_declared_symbol():
     assert b"null" in L.dl_last_error()
 
 
+def test_kernel_sources_read_no_environment():
+    """one library, no getenv, no study build — what runs depends on the call's arguments alone."""
+    csrc = os.path.join(ROOT, "druglamp_amd", "csrc")
+    files = sorted(os.listdir(csrc))
+    assert any(f.endswith(".hip") for f in files)
+    for f in files:
+        text = open(os.path.join(csrc, f)).read()
+        for word in ("getenv", "DL_STUDY", "dl_study_env"):
+            assert word not in text, "druglamp_amd/csrc/%s contains %s" % (f, word)
+
+
 @pytest.mark.parametrize("kind", ["DrugLAMP", "DrugLAMP2C2P", "DrugLAMPwoLLM"])
 def test_state_dict_abi_matches_reference(kind):
     from druglamp_amd.configs import get_cfg_defaults, load_yaml_into

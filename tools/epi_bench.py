@@ -1,4 +1,4 @@
-"""Epilogue cost study for the fat-N / small-K GEMMs: same shape with different epilogues and debug flags."""
+"""Epilogue cost study for the fat-N / small-K GEMMs: same shape with different epilogues."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from druglamp_amd import ops

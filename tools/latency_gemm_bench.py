@@ -1,8 +1,9 @@
 """Few-tile GEMM shapes of the strong-scaling batches (M = 8192 / 16384 / 32768 rows): gemm_kernel's two-buffer ring
-(DL_GEMM_LATCFG=0) against the deep-ring 128x128 forms of gemm_big_kernel (1: 128-byte rows x 4 stages, 2: x 3 stages,
-3: 64-byte rows x 4 stages, two workgroups per CU).  Study library; prints us per call and the max |diff| vs form 0."""
-import os, sys, time, torch
-os.environ["DL_USE_STUDY_LIB"] = "1"
+(algo=1) against what dl_gemm picks itself (algo=0: the deep-ring 128x128 form of gemm_big_kernel, 128-byte rows x 4
+stages, where eligible).  Prints us per call and the max |diff| between the two.  (The rejected ring forms — 3 stages,
+64-byte rows x 4 stages — were measured through the study build that existed up to commit 97fb613:
+profiles/r2_latency_gemm_bench.txt.)"""
+import sys, time, torch
 sys.path.insert(0, ".")
 from druglamp_amd import ops
 dt = torch.bfloat16
@@ -16,7 +17,7 @@ shapes = [(256, 1024, "brd"), (1024, 256, "bgpd"), (1024, 256, "G"), (256, 1024,
           (256, 256, "br"), (1536, 512, "b"), (512, 512, "br"), (512, 256, ""), (256, 256, ""), (128, 1152, "bg")]
 Ms = [int(a) for a in sys.argv[1:]] or [8192, 16384, 32768]
 for M in Ms:
-    print("M = %d%32s" % (M, "") + "".join("%9s" % ("cfg%d" % c) for c in range(4)) + "   max|diff|")
+    print("M = %d%32s" % (M, "") + "".join("%9s" % c for c in ("tile128", "auto")) + "   max|diff|")
     for (N, K, kw) in shapes:
         x = (torch.randn(M, K, device="cuda") * 0.5).to(dt); w = (torch.randn(N, K, device="cuda") * 0.1).to(dt); b = torch.randn(N, device="cuda")
         res = torch.randn(M, N, device="cuda").to(dt); pre = torch.empty(M, N, device="cuda", dtype=dt)
@@ -28,10 +29,9 @@ for M in Ms:
         if "r" in kw: k["residual"] = res
         if "G" in kw: k.update(dact_pre=res, dropout_p=0.1, seed=3)
         row, outs = [], []
-        for cfg in range(4):
-            os.environ["DL_GEMM_LATCFG"] = str(cfg)
+        for algo in (1, 0):
             out = torch.empty(M, N, device="cuda", dtype=dt)
-            row.append(t(lambda: ops.gemm(x, w, M=M, N=N, K=K, out=out, **k)))
+            row.append(t(lambda: ops.gemm(x, w, M=M, N=N, K=K, out=out, algo=algo, **k)))
             outs.append(out.float())
         d = max(float((o - outs[0]).abs().max()) for o in outs[1:])
         print("%-38s" % str((M, N, K, kw)) + "".join("%9.1f" % v for v in row) + "   %.2e" % d, flush=True)

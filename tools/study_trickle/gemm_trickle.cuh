@@ -1,8 +1,9 @@
 // gemm_trickle.cuh — the large-tile forward / data-gradient GEMM whose epilogue runs INSIDE the next tile's main loop
-// (round 6).  Included by gemm.hip after gemm_big.cuh (shares its LDS-DMA helpers and epilogue math).
+// (round 6).  Was included by gemm.hip after gemm_big.cuh (shares its LDS-DMA helpers and epilogue math).
 //
-// STATUS: STUDY LIBRARY ONLY (-DDL_STUDY, DL_GEMM_TRICKLE=1).  Correct (bit-identical to the other two kernels on every shape and
-// epilogue: tools/trickle_bench.py) and NOT faster: 5-25 % slower than gemm_big_kernel on the shapes of the path, a tie at K = 256
+// STATUS: NOT BUILT BY ANYTHING (see README.md next to this file).  It was part of the -DDL_STUDY library (DL_GEMM_TRICKLE=1) that
+// existed up to commit 97fb613.  Correct there (bit-identical to that library's other two kernels on every shape and epilogue:
+// tools/trickle_bench.py of that commit) and NOT faster: 5-25 % slower than gemm_big_kernel on the shapes of the path, a tie at K = 256
 // with the heavy epilogues.  The decomposition (tools/trickle_parts.py, profiles/r6_trickle_study.txt; 65536x2048x512 with GELU +
 // pre-activation + dropout): the trickled stores cost 27-33 us instead of the burst's 132 us — the mechanism works — but the
 // 256x128 main loop that leaves room for the parking area runs its k-steps at 40 % of the matrix pipe against the 256x256 tile's
@@ -34,8 +35,11 @@
 //
 // Numerics: the parked value is the bf16 ROUNDING of acc + bias — what the pre-activation / plain output stores anyway;
 // the GELU / gelu' / dropout / residual epilogues therefore act on that rounded value (as a chain of bf16 tensor ops
-// would).  gemm_kernel's and gemm_big_kernel's bf16 epilogues round at the same point (dl_round_store<T>), so the three
-// kernels stay bit-identical to each other (tests/test_kernels_gpu.py::test_large_tile_gemm_is_bitwise_equal_*).
+// would).  The PRODUCT kernels do not round there: gemm_kernel and gemm_big_kernel apply GELU / gelu' / dropout / residual to
+// the fp32 value of acc + bias (one rounding per output).  Only the study build made them round at the same point
+// (dl_round_store<T>, removed with that build) so that the three kernels could be compared bit for bit — which also means
+// that every timing A/B taken with the study library ran an epilogue the product does not run.  This kernel is therefore NOT
+// bit-identical to the product kernels on the GELU / gelu' / dropout / residual epilogues.
 //
 // Waits: vmcnt counts loads, LDS-DMA and stores in issue order (the compiler relies on the same rule for its own counted
 // waits on this target); the DMA instructions are inline assembly the compiler does not see, so every compiler-visible
