@@ -108,6 +108,19 @@ class AttnBwdArgs(C.Structure):
     ]
 
 
+class AttnProbsArgs(C.Structure):
+    _fields_ = [
+        ("Q", c_vp), ("K", c_vp), ("LSE", c_vp), ("out", c_vp), ("out_ld", c_i64),
+        ("q_ps", c_i64), ("q_hs", c_i64), ("q_rs", c_i64),
+        ("k_ps", c_i64), ("k_hs", c_i64), ("k_rs", c_i64),
+        ("n_problems", c_i32), ("n_heads", c_i32), ("n_segments", c_i32), ("partner_shift", c_i32),
+        ("Lq", c_i32), ("Lk", c_i32), ("head_dim", c_i32), ("dtype", c_i32),
+        ("scale", c_f32),
+        ("head_mean", c_i32), ("key_tail_rows", c_i32), ("key_tail_weight", c_f32), ("expand_tail", c_i32),
+        ("workspace", c_vp), ("workspace_bytes", c_sz),
+    ]
+
+
 class NtxentSide(C.Structure):
     _fields_ = [("q", c_vp), ("k", c_vp), ("n", c_i64), ("gid_offset", c_i64), ("lse", c_vp)]
 
@@ -144,6 +157,8 @@ SIGNATURES = {
                                  c_i32, c_i64, c_i64, c_i32, c_vp, c_sz, C.POINTER(ReduceItem), c_vp]),
     "dl_attn_fwd": (c_i32, [C.POINTER(AttnFwdArgs), c_vp]),
     "dl_attn_bwd": (c_i32, [C.POINTER(AttnBwdArgs), c_vp]),
+    "dl_attn_probs_workspace_bytes": (c_sz, [C.POINTER(AttnProbsArgs)]),
+    "dl_attn_probs": (c_i32, [C.POINTER(AttnProbsArgs), c_vp]),
     "dl_token_gate_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "dl_token_gate_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "dl_gate_dpre": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),

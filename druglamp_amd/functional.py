@@ -488,7 +488,8 @@ def layer_norm(x, weight, bias, eps):
 # ------------------------------------------------------------------------------------------------
 class GuidedCrossAttentionFn(torch.autograd.Function):
     """query (Lq, B, E), key == value (Lk, B, E), seq-first as the reference passes them.
-    Returns (out (Lq, B, E), raw logits (B, H, Lq, Lk) fp32 or None).
+    Returns (out (Lq, B, E), raw logits (B, H, Lq, Lk) fp32 or None); with need_probs the second output is the head-averaged
+    softmax map (B, Lq, Lk_out) fp32 instead (non-differentiable, as the raw logits are), Lk_out = the full key count.
     key_tail = (rows, weight) (round 5): `key` holds only the DISTINCT key rows of the reference's 512 — the batch's block of
     real nodes / tokens followed by `rows` rows that each stand for `weight` identical padding rows (MolecularGCN's and the
     drug LLM adaptor's compact forms hand them over before their expansion).  The attention adds log(weight) to those keys'
@@ -499,7 +500,9 @@ class GuidedCrossAttentionFn(torch.autograd.Function):
     products, and a tail row's dkv is already the sum over its copies, so its product counts once — no extra factor."""
 
     @staticmethod
-    def forward(ctx, query, key, in_w, in_b, out_w, out_b, H, need_raw, key_tail=None):
+    def forward(ctx, query, key, in_w, in_b, out_w, out_b, H, need_raw, key_tail=None, need_probs=False):
+        if need_raw and need_probs:
+            raise ValueError("GuidedCrossAttentionFn: need_raw and need_probs are alternatives for the second output")
         Lq, B, E = query.shape
         Lk = key.shape[0]
         cdt = query.dtype
@@ -520,6 +523,12 @@ class GuidedCrossAttentionFn(torch.autograd.Function):
                            head_dim=hd, scale=scale, q_strides=(Lq * E, hd, E), k_strides=(Lk * 2 * E, hd, 2 * E),
                            v_strides=(Lk * 2 * E, hd, 2 * E), out=o, o_strides=(Lq * E, hd, E), o_ss=0, raw_logits=raw,
                            key_tail=key_tail)
+        if need_probs:
+            # the head-averaged map from the projections and the forward's statistics (dl_attn_probs); with key_tail one column per
+            # row of the FULL key set, in ExpandTailFn's order
+            raw = ops.attn_probs(qp, kv, lse=lse, head_mean=True, key_tail=key_tail, expand_tail=key_tail is not None,
+                                 n_problems=B, n_heads=H, n_segments=1, partner_shift=0, Lq=Lq, Lk=Lk, head_dim=hd, scale=scale,
+                                 q_strides=(Lq * E, hd, E), k_strides=(Lk * 2 * E, hd, 2 * E))[0]
         ow = lowp((out_w,), cdt)
         y = ops.gemm(o, ow, M=B * Lq, N=E, K=E, bias=_f32(out_b))
         # [in][out] images for the data gradients (K-contiguous products; the K-slow forward images otherwise)
@@ -560,7 +569,7 @@ class GuidedCrossAttentionFn(torch.autograd.Function):
         else:
             dquery = ops.gemm(dqp, w[:E], M=Lq * B, N=E, K=E, w_kslow=True, ldw=E).view(B, Lq, E).transpose(0, 1)
             dkey = ops.gemm(dkv, w[E:], M=Lk * B, N=E, K=2 * E, w_kslow=True, ldw=E).view(B, Lk, E).transpose(0, 1)
-        return dquery, dkey, din_w, din_b, dwo, dbo, None, None, None
+        return dquery, dkey, din_w, din_b, dwo, dbo, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------

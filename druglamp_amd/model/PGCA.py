@@ -4,7 +4,7 @@ GuidedCrossAttention keeps the reference's constructor, seq-first forward signat
 keys (in_proj_weight / in_proj_bias / out_proj.*).  The path the DrugLAMP models take — key is value,
 no masks, dropout 0, need_weights & need_raw — runs as in-proj GEMMs + one fused attention launch +
 out-proj GEMM; the raw (pre-softmax) logits the reference returns as its second output are written by
-the same attention launch.  Other argument combinations of the torch-1.x MultiheadAttention fork
+the same attention launch, the head-averaged softmax weights (need_raw=False) by dl_attn_probs.  Other argument combinations of the torch-1.x MultiheadAttention fork
 (masks, bias_kv, zero-attn, separate kdim/vdim) are not on the path and raise.
 """
 from __future__ import annotations
@@ -41,7 +41,11 @@ class GuidedCrossAttention(nn.Module):
     def forward(self, query, key, value, key_padding_mask=None, need_weights=True, need_raw=True, attn_mask=None, key_tail=None):
         """key_tail = (rows, weight) (not in the reference's signature; default None = the reference's call): `key` holds the
         distinct key rows only, its last `rows` rows each standing for `weight` identical rows of the full key set
-        (functional.GuidedCrossAttentionFn).  The raw logits are those of the full key set and are not produced then."""
+        (functional.GuidedCrossAttentionFn).  The raw logits are those of the full key set and are not produced then.
+        need_weights and not need_raw: the second output is the stock MultiheadAttention's, the softmax weights averaged over
+        the heads, (bsz, tgt_len, S) fp32 with S the FULL key count (with key_tail: the distinct rows followed by the tail's
+        copies in functional.ExpandTailFn's order).  They are DETACHED: the reference's weights are differentiable, but nothing
+        on the DrugLAMP path differentiates them."""
         if key_padding_mask is not None or attn_mask is not None:
             raise NotImplementedError("GuidedCrossAttention: masks are not on the DrugLAMP path")
         if not (key is value or (key.data_ptr() == value.data_ptr() and key.shape == value.shape
@@ -54,10 +58,9 @@ class GuidedCrossAttention(nn.Module):
         want_raw = bool(need_weights and need_raw)
         if key_tail is not None and want_raw:
             raise ValueError("GuidedCrossAttention: raw logits are not available with key_tail (pass need_weights=False)")
-        if need_weights and not need_raw:
-            raise NotImplementedError("GuidedCrossAttention: head-averaged softmax weights are not implemented")
+        want_probs = bool(need_weights and not need_raw)
         q = Fn.cast(query, self.compute_dtype)
         k = Fn.cast(key, self.compute_dtype)
         out, raw = Fn.GuidedCrossAttentionFn.apply(q, k, self.in_proj_weight, self.in_proj_bias, self.out_proj.weight,
-                                                   self.out_proj.bias, self.num_heads, want_raw, key_tail)
+                                                   self.out_proj.bias, self.num_heads, want_raw, key_tail, want_probs)
         return Fn.cast(out, query.dtype), raw

@@ -336,6 +336,10 @@ class DrugLAMPBase(nn.Module):
         self.A_x_gca = None
         self.attn, self.guide_attn = [], []
         self.keep_raw_attention = True
+        # True: the PGCA blocks hand back their softmax weights (B, 256, 512) instead of the raw logits — kept on P_*_gca for
+        # get_cross_attn_prob, A_*_gca stay None.  Detached; written by dl_attn_probs, also from the compact-key form.
+        self.keep_attention_probs = False
+        self.P_v_gca = self.P_x_gca = None
         self.compute_dtype = torch.float32
 
     # ---- precision ---------------------------------------------------------------------------
@@ -365,11 +369,13 @@ class DrugLAMPBase(nn.Module):
         return t.view(-1, self.site_len, n_site, t.size(-1)).mean(dim=1)
 
     def _gca_branch(self, gca, mhla, norm, prot_sites, drug_nodes, raw=True, tail=None):
-        """PGCA -> concat -> MHLA + residual -> LayerNorm (DrugLAMP.py:55-71).  Returns (m, raw logits).
+        """PGCA -> concat -> MHLA + residual -> LayerNorm (DrugLAMP.py:55-71).  Returns (m, raw logits), or with
+        keep_attention_probs (m, softmax weights (B, 256, 512)) whatever `raw` says; _keep_map stores the second output.
         raw=False (BatchHints.raw_attention, the trainer's steps): the (B, 1, 256, 512) fp32 pre-softmax logits the reference
         keeps on self.A_*_gca for get_cross_attn_mat (basic_model.py:123-129) are not written — 134 MB per branch and step at
         batch 256 that nothing in a training step reads."""
-        want_raw = self.keep_raw_attention and raw
+        probs = self.keep_attention_probs
+        want_raw = self.keep_raw_attention and raw and not probs
         if tail is not None and not want_raw and self.compact_keys:
             # Round 5: the drug side arrives from a compact padding form (MolecularGCN / the drug LLM adaptor: a block of
             # real rows + 8 rows that each stand for w identical padding rows).  The cross-attention runs over those distinct
@@ -379,10 +385,10 @@ class DrugLAMPBase(nn.Module):
             if keys.dtype != drug_nodes.dtype:
                 keys = Fn.cast(keys, drug_nodes.dtype)
             kt = keys.permute(1, 0, 2)
-            m, raw = gca(prot_sites.permute(1, 0, 2), kt, kt, need_weights=False, need_raw=True, key_tail=(_TAIL_ROWS, w))
+            m, raw = gca(prot_sites.permute(1, 0, 2), kt, kt, need_weights=probs, need_raw=not probs, key_tail=(_TAIL_ROWS, w))
         else:
             m, raw = gca(prot_sites.permute(1, 0, 2), drug_nodes.permute(1, 0, 2), drug_nodes.permute(1, 0, 2),
-                         need_weights=want_raw, need_raw=True)
+                         need_weights=want_raw or probs, need_raw=not probs)
         g = m.permute(1, 0, 2)
         if prot_sites.dtype != g.dtype:
             prot_sites = Fn.cast(prot_sites, g.dtype)
@@ -392,6 +398,13 @@ class DrugLAMPBase(nn.Module):
         # no fp32 round trips between PGCA, MHLA, LayerNorm and PMMA
         m = Fn.layer_norm(m, norm.weight, norm.bias, norm.eps)
         return m, raw
+
+    def _keep_map(self, modality, m, amap):
+        """Stores a _gca_branch's second output where its getter looks for it (A_*_gca: raw logits, P_*_gca: weights); returns m."""
+        probs = self.keep_attention_probs
+        setattr(self, "A_%s_gca" % modality, None if probs else amap)
+        setattr(self, "P_%s_gca" % modality, amap if probs else None)
+        return m
 
     def _ssl_drug_rows(self, vtail, xtail):
         """The block size behind which BOTH drug tensors of the SSL head (MolecularGCN output, fill-augmented LLM features) are
@@ -445,6 +458,15 @@ class DrugLAMPBase(nn.Module):
             return self.A_v_gca
         self.A_x_gca = self.A_x_gca.cpu()
         return self.A_x_gca
+
+    def get_cross_attn_prob(self, modality="v"):
+        """The softmax weights of the PGCA block of `modality` from the last forward with keep_attention_probs, (B, 256, 512) on the CPU."""
+        name = "P_v_gca" if modality == "v" else "P_x_gca"
+        p = getattr(self, name)
+        if p is None:
+            raise RuntimeError("get_cross_attn_prob: no map kept — set keep_attention_probs = True before the forward")
+        setattr(self, name, p.cpu())
+        return getattr(self, name)
 
     def get_inter_attn_mat(self):
         return self.attn, self.guide_attn

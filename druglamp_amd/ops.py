@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, GemmArgs, check
+from ._lib import DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, check
 
 _DT = {torch.float32: DL_F32, torch.bfloat16: DL_BF16}
 
@@ -416,6 +416,49 @@ def attn_bwd(q, k, v, o, do, lse, *, n_problems, n_heads, n_segments, partner_sh
     if key_tail is not None:
         a.key_tail_rows, a.key_tail_weight = int(key_tail[0]), float(key_tail[1])
     check(_lib.lib().dl_attn_bwd(C.byref(a), _stream()), "dl_attn_bwd")
+
+
+def attn_probs(q, k, *, n_problems, n_heads, n_segments, partner_shift, Lq, Lk, head_dim, scale, q_strides, k_strides,
+               lse=None, head_mean=False, key_tail=None, expand_tail=False, out=None, out_ld=None):
+    """The attention probability map softmax(scale q k^T) in fp32 (dl_attn_probs): Q / K addressed as in attn_fwd.
+    Returns (S, P, Lq, cols) with head_mean, (S, P, H, Lq, cols) otherwise; cols = Lk, or with key_tail = (rows, weight) and
+    expand_tail the full key count Lk - rows + rows * weight in functional.ExpandTailFn's order.  lse: the LSE of an attn_fwd
+    call on the same q, k, scale and key_tail; None = computed here into a workspace.  out / out_ld (elements): write into
+    this buffer with this row pitch instead (the same rows, out_ld apart; returns `out`)."""
+    _need_gpu(q, k, lse, out)
+    a = AttnProbsArgs()
+    a.Q, a.K, a.LSE = q.data_ptr(), k.data_ptr(), _ptr(lse)
+    a.q_ps, a.q_hs, a.q_rs = q_strides
+    a.k_ps, a.k_hs, a.k_rs = k_strides
+    a.n_problems, a.n_heads, a.n_segments, a.partner_shift = n_problems, n_heads, n_segments, partner_shift
+    a.Lq, a.Lk, a.head_dim, a.dtype = Lq, Lk, head_dim, _dt(q)
+    a.scale = float(scale)
+    a.head_mean, a.expand_tail = int(bool(head_mean)), int(bool(expand_tail))
+    cols = Lk
+    if key_tail is not None:
+        a.key_tail_rows, a.key_tail_weight = int(key_tail[0]), float(key_tail[1])
+        if expand_tail:
+            cols = Lk - int(key_tail[0]) + int(key_tail[0]) * int(key_tail[1])
+    if lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != n_segments * n_problems * n_heads * Lq):
+        raise ValueError("attn_probs: lse must be a contiguous float32 tensor of (n_segments, n_problems, n_heads, Lq)")
+    if out is None:
+        shape = (n_segments, n_problems, Lq, cols) if head_mean else (n_segments, n_problems, n_heads, Lq, cols)
+        out = torch.empty(shape, dtype=torch.float32, device=q.device)
+        out_ld = cols
+    else:
+        rows = n_segments * n_problems * (1 if head_mean else n_heads) * Lq
+        if out.dtype != torch.float32 or out_ld is None or not out.is_contiguous() or out.device != q.device:
+            raise ValueError("attn_probs: out must be a contiguous float32 tensor on q's device and come with its row pitch out_ld")
+        if out_ld < cols or out.numel() < (rows - 1) * int(out_ld) + cols:
+            raise ValueError("attn_probs: out holds %d elements, %d rows of %d columns at pitch %d need %d"
+                             % (out.numel(), rows, cols, out_ld, (rows - 1) * int(out_ld) + cols))
+    a.out, a.out_ld = out.data_ptr(), int(out_ld)
+    L = _lib.lib()
+    if lse is None:
+        ws = _ws.get(L.dl_attn_probs_workspace_bytes(C.byref(a)), q.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(L.dl_attn_probs(C.byref(a), _stream()), "dl_attn_probs")
+    return out
 
 
 def dropout_apply(x2d: torch.Tensor, p: float, seed: int) -> torch.Tensor:

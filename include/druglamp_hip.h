@@ -308,6 +308,43 @@ typedef struct {
 } dl_attn_bwd_args;
 int dl_attn_bwd(const dl_attn_bwd_args* a, dl_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Attention probability maps: out = softmax(scale * Q K^T) as fp32, V never touched.
+ *
+ * What the reference hands back for interpretation: GuidedCrossAttention's attn_output_weights
+ * (guided_cross_attention_model.py:307-327 — the softmax at 308, the mean over heads at 324-327 when
+ * need_weights and not need_raw) and the `weights` the PMMA Attention returns under vis=True
+ * (model/PMMA/attention.py: attention_probs of paired_attention / forward).
+ *
+ * Problems, segments, heads and the Q / K addressing are dl_attn_fwd's (q_*, k_* strides,
+ * partner_shift).  P[q][k] = exp(scale q.k + log w_k - LSE_q) with the LSE layout of dl_attn_fwd:
+ * LSE may be the one a dl_attn_fwd call wrote for the same Q, K, scale and key tail (workspace may
+ * then be NULL); with LSE == NULL the call first computes the statistics into `workspace`
+ * (dl_attn_probs_workspace_bytes: n_segments * n_problems * n_heads * Lq floats).
+ * Output rows have a pitch of out_ld ELEMENTS (>= the column count); nothing beyond a row's columns is written:
+ *   head_mean == 0: row ((seg * n_problems + p) * n_heads + h) * Lq + q holds head h's map
+ *   head_mean == 1: row (seg * n_problems + p) * Lq + q holds (1 / n_heads) sum_h P_h, summed in ascending h
+ *                   (no atomics: bitwise repeatable)
+ * Key multiplicities (key_tail_rows = t, key_tail_weight = w, one segment, as dl_attn_fwd; lead = Lk - t):
+ *   expand_tail == 0: Lk columns, the softmax over the DISTINCT keys — a tail key's column carries the mass
+ *                     of the w keys it stands for (any w >= 1)
+ *   expand_tail == 1: lead + t * w columns, the map over the FULL key set in the order the host's expansion
+ *                     of the tail uses: column lead + i * t + j (i < w, j < t) holds the probability of ONE
+ *                     copy of tail key j, exp(scale q.k_{lead+j} - LSE_q).  w must be a whole number.
+ * head_dim in {64, 128}; Q / K 16-byte aligned with strides multiples of 16 bytes; Lq, Lk arbitrary.
+ * 16-byte stores when out is 16-byte aligned and out_ld a multiple of 4, 4-byte stores otherwise.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* Q; const void* K; const float* LSE; float* out; int64_t out_ld;
+  int64_t q_ps, q_hs, q_rs, k_ps, k_hs, k_rs;
+  int32_t n_problems, n_heads, n_segments, partner_shift, Lq, Lk, head_dim, dtype;
+  float scale;
+  int32_t head_mean, key_tail_rows; float key_tail_weight; int32_t expand_tail;
+  void* workspace; size_t workspace_bytes;
+} dl_attn_probs_args;
+size_t dl_attn_probs_workspace_bytes(const dl_attn_probs_args* a);
+int dl_attn_probs(const dl_attn_probs_args* a, dl_stream s);
+
 
 /* ------------------------------------------------------------------------------------------
  * MHLA token gate (MultiHeadLinearAttention.forward, model/PMMA/encoder.py:127-140):
