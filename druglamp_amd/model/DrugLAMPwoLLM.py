@@ -5,6 +5,8 @@ from .basic_model import DrugLAMPBase
 
 
 class DrugLAMPwoLLM(DrugLAMPBase):
+    llm_branch = False
+
     def __init__(self, n_drug_feature, n_prot_feature, n_hidden=128, **cfg):
         super().__init__(n_drug_feature, n_prot_feature, n_hidden, **cfg)
 

@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, check
+from ._lib import DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, PgcaPairsArgs, check
 
 _DT = {torch.float32: DL_F32, torch.bfloat16: DL_BF16}
 
@@ -461,6 +461,55 @@ def attn_probs(q, k, *, n_problems, n_heads, n_segments, partner_shift, Lq, Lk, 
     return out
 
 
+def pgca_pairs(q, kv, q_index, kv_index, *, scale, left=None, bias=None, key_tail=None, out=None):
+    """The pair-indexed PGCA attention core over cached entity codes (dl_pgca_pairs_fwd).  q (n_q, Lq, 128): the projected
+    queries per protein; kv (n_kv, Lk, 256) = [K | V']: the projected keys and the values behind the out-projection per drug
+    (screening.DrugCode); q_index / kv_index (n_pairs,) int32 device tensors.  Pair n gets softmax(scale q[qi] k[ki]^T) v'[ki]
+    (+ bias, fp32 (128,)) at columns left_cols.. of out[n], and left[qi] (n_q, Lq, left_cols) bit for bit in front of it.
+    Entities may be views with any 16-byte-aligned entity and row strides (columns contiguous).  out (n_pairs, Lq, left_cols
+    + 128) is allocated unless given; a caller's out may have wider rows.  key_tail = (rows, weight) as in attn_fwd.  A pair
+    with an index out of range is skipped and sets FLAG_PAIR_INDEX in the device guard word (check_guard_flags)."""
+    _need_gpu(q, kv, q_index, kv_index, left, bias, out)
+    if q.dim() != 3 or kv.dim() != 3 or q.shape[2] != 128 or kv.shape[2] != 256 or q.stride(2) != 1 or kv.stride(2) != 1:
+        raise ValueError("pgca_pairs: q must be (n_q, Lq, 128) and kv (n_kv, Lk, 256) with contiguous columns")
+    if kv.dtype != q.dtype:
+        raise ValueError("pgca_pairs: q is %s, kv is %s" % (q.dtype, kv.dtype))
+    for t in (q_index, kv_index):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != q_index.numel():
+            raise ValueError("pgca_pairs: q_index / kv_index must be contiguous int32 vectors of one length")
+    n_pairs, (n_q, Lq, E), (n_kv, Lk, _) = q_index.numel(), q.shape, kv.shape
+    left_cols = 0
+    if left is not None:
+        if left.dim() != 3 or left.shape[:2] != q.shape[:2] or left.dtype != q.dtype or left.stride(2) != 1:
+            raise ValueError("pgca_pairs: left must be (n_q, Lq, cols) of q's dtype with contiguous columns")
+        left_cols = left.shape[2]
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != E or not bias.is_contiguous()):
+        raise ValueError("pgca_pairs: bias must be a contiguous float32 vector of %d" % E)
+    cols = left_cols + E
+    if out is None:
+        out = torch.empty((n_pairs, Lq, cols), dtype=q.dtype, device=q.device)
+    elif (out.dim() != 3 or out.dtype != q.dtype or out.device != q.device or out.shape[0] != n_pairs or out.shape[1] != Lq
+          or out.shape[2] < cols or out.stride(2) != 1 or out.stride(1) < cols or (n_pairs > 1 and out.stride(0) < (Lq - 1) * out.stride(1) + cols)):
+        raise ValueError("pgca_pairs: out must be a %s tensor of (%d, %d, >= %d) on q's device with contiguous columns and "
+                         "non-overlapping rows (got %s, strides %s)" % (q.dtype, n_pairs, Lq, cols, tuple(out.shape), out.stride()))
+    a = PgcaPairsArgs()
+    a.Q, a.K, a.V, a.left, a.out, a.bias = q.data_ptr(), kv.data_ptr(), kv.data_ptr() + E * kv.element_size(), _ptr(left), out.data_ptr(), _ptr(bias)
+    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
+    a.q_es, a.q_rs = q.stride(0), q.stride(1)
+    a.k_es, a.k_rs = kv.stride(0), kv.stride(1)
+    a.v_es, a.v_rs = kv.stride(0), kv.stride(1)
+    if left is not None:
+        a.left_es, a.left_rs = left.stride(0), left.stride(1)
+    a.out_ps, a.out_rs = out.stride(0), out.stride(1)
+    a.n_pairs, a.n_q, a.n_kv, a.Lq, a.Lk, a.head_dim, a.dtype = n_pairs, n_q, n_kv, Lq, Lk, E, _dt(q)
+    a.left_cols, a.out_col0 = left_cols, left_cols
+    a.scale = float(scale)
+    if key_tail is not None:
+        a.key_tail_rows, a.key_tail_weight = int(key_tail[0]), float(key_tail[1])
+    check(_lib.lib().dl_pgca_pairs_fwd(C.byref(a), _stream()), "dl_pgca_pairs_fwd")
+    return out
+
+
 def dropout_apply(x2d: torch.Tensor, p: float, seed: int) -> torch.Tensor:
     y = torch.empty_like(x2d)
     rows, D = x2d.shape
@@ -900,7 +949,9 @@ FLAG_TEXT = {_lib.FLAG_PROT_PERIOD: "a protein's residue codes / fill bits are n
              _lib.FLAG_GCN_NODE_PAD: "drug graph nodes beyond the adjacency block are not identical virtual padding nodes "
                                      "(handler/dataset.py:216-221); disable with DL_GCN_COMPACT=0",
              _lib.FLAG_PLAN_ROWS: "the ProteinCNN row tables were built with fewer rows than the batch's residue counts need "
-                                  "(dl_protein_plan_build capacity)"}
+                                  "(dl_protein_plan_build capacity)",
+             _lib.FLAG_PAIR_INDEX: "a (protein, drug) pair of a screening launch names an entity outside the cached codes; the pair "
+                                   "was skipped (dl_pgca_pairs_fwd)"}
 
 
 def guard_flags(device) -> torch.Tensor:

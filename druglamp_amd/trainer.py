@@ -950,6 +950,36 @@ class Trainer:
         self.check_device_flags()
         return p, y, loss_sum, p.numel()
 
+    @torch.no_grad()
+    def screen(self, protein_batches, drug_batches, pair_batch: int = 256) -> torch.Tensor:
+        """Library screening: the (P, D) fp32 probabilities `predict` would give for every (protein, drug) pair, with the
+        per-entity part of the forward paid once per protein and once per drug (druglamp_amd/screening.py).
+        protein_batches yields (feat_p, llm_p), drug_batches yields (feat_d, llm_d) as the collate hands them over (llm_d is None
+        for a model without an LLM branch; llm_p is always needed: the fill bit comes from it).  The protein codes stay
+        resident; the drug batches are streamed — encode one, score it against every protein in chunks of pair_batch pairs, drop
+        its code — so memory is bounded by one drug batch whatever the library size.  Inside a chunk the pairs are ordered
+        drug-major: consecutive workgroups of the attention launch share a drug's K | V' in L2."""
+        from .screening import ProteinCode
+        if pair_batch < 1:
+            raise ValueError("screen: pair_batch must be positive")
+        self.model.eval()
+        pcode = ProteinCode.cat([self.model.encode_proteins(feat_p, llm_p) for feat_p, llm_p in protein_batches])
+        P = pcode.n
+        cols = []
+        for feat_d, llm_d in drug_batches:
+            dcode = self.model.encode_drugs(feat_d, llm_d)
+            Dn = dcode.n
+            di = torch.arange(Dn).repeat_interleave(P)          # drug-major
+            pi = torch.arange(P).repeat(Dn)
+            scores = [self.model.score_codes(pcode, dcode, pi[s:s + pair_batch], di[s:s + pair_batch]) for s in range(0, Dn * P, pair_batch)]
+            score = torch.cat(scores)
+            prob = torch.sigmoid(score).squeeze(1) if self.n_class == 1 else torch.softmax(score, dim=1)[:, 1]
+            cols.append(prob.view(Dn, P).t())
+            del dcode
+        out = torch.cat(cols, dim=1).contiguous() if cols else torch.zeros((P, 0), dtype=torch.float32, device=self.device)
+        self.check_device_flags()
+        return out
+
     def evaluate(self, batches) -> Dict[str, float]:
         """Metrics over the union of all ranks' samples (the reference's torchmetrics objects gather their states at
         epoch end, trainer.py:262-292; its logged loss is `sync_dist=True`): ranks may hold different numbers of samples."""

@@ -345,6 +345,42 @@ typedef struct {
 size_t dl_attn_probs_workspace_bytes(const dl_attn_probs_args* a);
 int dl_attn_probs(const dl_attn_probs_args* a, dl_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Pair-indexed PGCA attention core (forward only): the screening path's cross attention over
+ * cached per-entity operands.
+ *
+ * GuidedCrossAttention's key-is-value branch (guided_cross_attention_model.py:138-162,290-314) projects
+ * the query from the protein alone and key / value from the drug alone, and its out-projection is
+ * linear behind the softmax: softmax(Q K^T) V W_o^T = softmax(Q K^T) (V W_o^T).  So Q is kept per
+ * protein, K and V' = V W_o^T per drug, and a (protein, drug) pair needs only the core below.
+ *
+ * For pair n < n_pairs with p = q_index[n], d = kv_index[n] (int32, device memory):
+ *   S = scale * Q[p] K[d]^T  (+ log key_tail_weight on the last key_tail_rows keys, as dl_attn_fwd)
+ *   O = softmax(S) V[d]  (+ bias[c] in column c, fp32, if bias is given)
+ *   out (n, r, out_col0 + c) = O[r][c]         c < head_dim, r < Lq
+ *   out (n, r, c)            = left (p, r, c)  c < left_cols (bitwise copy; only with left != NULL)
+ * Addressing (element strides, all tensors dtype `dtype`, columns contiguous):
+ *   q    (e, r, :) = Q + e*q_es + r*q_rs          e < n_q    (K, V: k_*, v_*, e < n_kv, r < Lk)
+ *   left (e, r, :) = left + e*left_es + r*left_rs  e < n_q
+ *   out  (n, r, :) = out + n*out_ps + r*out_rs
+ * Nothing is written outside the addressed columns of the addressed rows.
+ * A pair whose index is outside [0, n_q) or [0, n_kv) is skipped — nothing is read through the index,
+ * nothing is written for the pair — and DL_FLAG_PAIR_INDEX is OR-ed into *flags (flags may be NULL).
+ * One head, head_dim == 128 (else DL_ERR_UNSUPPORTED); Lq, Lk arbitrary (tails are masked); pointers 16-byte
+ * aligned, strides multiples of 16 bytes; left_cols and out_col0 multiples of 8 elements, left_cols <= out_col0;
+ * key_tail_rows <= Lk, key_tail_weight >= 1.  n_pairs == 0: DL_OK, nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* Q; const void* K; const void* V; const void* left; void* out; const float* bias;
+  const int32_t* q_index; const int32_t* kv_index; uint32_t* flags;
+  int64_t q_es, q_rs, k_es, k_rs, v_es, v_rs, left_es, left_rs, out_ps, out_rs;
+  int32_t n_pairs, n_q, n_kv, Lq, Lk, head_dim, dtype;
+  int32_t left_cols, out_col0;
+  float scale;
+  int32_t key_tail_rows; float key_tail_weight;
+} dl_pgca_pairs_args;
+int dl_pgca_pairs_fwd(const dl_pgca_pairs_args* a, dl_stream s);
+
 
 /* ------------------------------------------------------------------------------------------
  * MHLA token gate (MultiHeadLinearAttention.forward, model/PMMA/encoder.py:127-140):
@@ -430,7 +466,8 @@ int dl_embed_pad(const int64_t* ids, const void* weight, const void* fill, void*
                  int32_t V, int32_t D, int32_t halo, int32_t dtype, dl_stream s);
 /* Device-side guard flags (sticky bits OR-ed into a caller-owned uint32 word; the trainer polls it):
  * the compact forms below are only valid for inputs with the padding structure of the reference's collate. */
-enum { DL_FLAG_PROT_PERIOD = 1, DL_FLAG_DRUG_TOKEN_PAD = 2, DL_FLAG_GCN_NODE_PAD = 4, DL_FLAG_PLAN_ROWS = 8 };
+enum { DL_FLAG_PROT_PERIOD = 1, DL_FLAG_DRUG_TOKEN_PAD = 2, DL_FLAG_GCN_NODE_PAD = 4, DL_FLAG_PLAN_ROWS = 8,
+       DL_FLAG_PAIR_INDEX = 16 /* dl_pgca_pairs_fwd: a pair's entity index is out of range (the pair was skipped) */ };
 /* ProteinCNN head on distinct rows (round 4; model/basic_model.py:168-171 over a sequence tiled by utils.py:392-412):
  * out[r][:D] = weight[ids[src[r]]], out[r][D] = fill[src[r]] for src[r] >= 0 (a flat index into ids / fill [B * L]), a zero
  * row for src[r] < 0.  weight padded to [V][D + 1] as for dl_embed_pad.  With `period` [B] given the same launch checks
