@@ -508,23 +508,41 @@ class DrugLAMPBase(nn.Module):
         """Scores (N, n_out) fp32 of the pairs (pi[n], di[n]) of cached codes: per branch ONE ops.pgca_pairs launch writes the
         (N, n_site, 256) [sites | guided] concat, then MHLA + residual, LayerNorm, PMMA, token mean and the classifier exactly
         as in the forward.  pi / di: host index sequences (list, numpy array, CPU tensor), range-checked here."""
-        self._need_eval("score_codes")
-        for code, what in ((pcode, "protein"), (dcode, "drug")):
+        def attend(name, gca, q, sites, pi_d, di_d):
+            d = dcode.branches[name]
+            return ops.pgca_pairs(q, d.kv, pi_d, di_d, scale=float(gca.head_dim) ** -0.5, left=sites, bias=d.bias, key_tail=d.key_tail)
+        return self._score_pairs("score_codes", pcode, dcode, "code", pi, di, attend)
+
+    @torch.no_grad()
+    def score_library(self, pcode, lib, pi, di) -> torch.Tensor:
+        """score_codes against a resident screening.DrugLibrary: the same contract and checks, with ONE ops.pgca_pairs_ragged
+        launch per branch (every drug attends over its own trimmed keys) in front of the same tail."""
+        def attend(name, gca, q, sites, pi_d, di_d):
+            b = lib.branches[name]
+            return ops.pgca_pairs_ragged(q, b.rows, b.row0, b.n_keys, b.tail_weight, pi_d, di_d, scale=float(gca.head_dim) ** -0.5,
+                                         key_tail_rows=screening.LIB_TAIL_ROWS, left=sites, bias=b.bias)
+        return self._score_pairs("score_library", pcode, lib, "library", pi, di, attend)
+
+    def _score_pairs(self, who, pcode, dcode, dwhat, pi, di, attend) -> torch.Tensor:
+        """The pair stage behind score_codes / score_library: the checks, attend() per branch for the [sites | guided] concat,
+        and the MHLA -> LayerNorm -> PMMA -> token mean -> classifier tail."""
+        self._need_eval(who)
+        for code, what in ((pcode, "protein code"), (dcode, "drug " + dwhat)):
             if code.dtype != self.compute_dtype:
-                raise RuntimeError("score_codes: the %s code was built in %s, the model computes in %s" % (what, code.dtype, self.compute_dtype))
+                raise RuntimeError("%s: the %s was built in %s, the model computes in %s" % (who, what, code.dtype, self.compute_dtype))
             if code.epoch != screening.param_epoch():
-                raise RuntimeError("score_codes: the %s code was built before the parameters last changed (parameter epoch %d, now %d); "
-                                   "encode again" % (what, code.epoch, screening.param_epoch()))
+                raise RuntimeError("%s: the %s was built before the parameters last changed (parameter epoch %d, now %d); "
+                                   "encode again" % (who, what, code.epoch, screening.param_epoch()))
         if set(pcode.branches) != set(dcode.branches) or ("x" in pcode.branches) != self.llm_branch:
-            raise RuntimeError("score_codes: the codes' branches do not match the model's")
+            raise RuntimeError("%s: the codes' branches do not match the model's" % who)
         pi_t = torch.as_tensor(pi, dtype=torch.int64, device="cpu").reshape(-1)
         di_t = torch.as_tensor(di, dtype=torch.int64, device="cpu").reshape(-1)
         if pi_t.numel() != di_t.numel():
-            raise ValueError("score_codes: %d protein indices, %d drug indices" % (pi_t.numel(), di_t.numel()))
+            raise ValueError("%s: %d protein indices, %d drug indices" % (who, pi_t.numel(), di_t.numel()))
         N = pi_t.numel()
         for t, n, what in ((pi_t, pcode.n, "protein"), (di_t, dcode.n, "drug")):
             if N and (int(t.min()) < 0 or int(t.max()) >= n):
-                raise IndexError("score_codes: %s index out of range [0, %d)" % (what, n))
+                raise IndexError("%s: %s index out of range [0, %d)" % (who, what, n))
         dev = pcode.branches["v"][1].device
         n_out = self.mlp_classifier.fc4.out_features
         if N == 0:
@@ -535,8 +553,7 @@ class DrugLAMPBase(nn.Module):
             if name not in pcode.branches:
                 continue
             sites, q = pcode.branches[name]
-            d = dcode.branches[name]
-            cat = ops.pgca_pairs(q, d.kv, pi_d, di_d, scale=float(gca.head_dim) ** -0.5, left=sites, bias=d.bias, key_tail=d.key_tail)
+            cat = attend(name, gca, q, sites, pi_d, di_d)
             h = mhla(cat, add_residual=True)
             m[name] = Fn.layer_norm(h, norm.weight, norm.bias, norm.eps)
         f, _, _ = self.pmma(m["x"], m["v"]) if self.llm_branch else self.pmma(m["v"], m["v"])

@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, PgcaPairsArgs, check
+from ._lib import DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, PgcaPairsArgs, PgcaPairsRaggedArgs, check
 
 _DT = {torch.float32: DL_F32, torch.bfloat16: DL_BF16}
 
@@ -510,6 +510,60 @@ def pgca_pairs(q, kv, q_index, kv_index, *, scale, left=None, bias=None, key_tai
     return out
 
 
+def pgca_pairs_ragged(q, rows, row0, n_keys, tail_weight, q_index, kv_index, *, scale, key_tail_rows, left=None, bias=None, out=None):
+    """pgca_pairs over a packed per-drug row store (dl_pgca_pairs_ragged_fwd; screening.DrugLibrary).  q (n_q, Lq, 128) as in
+    pgca_pairs; rows (R, 256) = [K | V'] of every drug back to back; drug d owns rows row0[d] .. row0[d] + n_keys[d] - 1, and
+    each of its last key_tail_rows rows (launch-wide) stands for tail_weight[d] >= 1 identical keys.  row0 int64, n_keys int32,
+    tail_weight float32: contiguous device vectors of one length (the number of drugs).  left / bias / out as in pgca_pairs.
+    A pair with an index out of range sets FLAG_PAIR_INDEX, one whose drug's table entry does not describe rows inside
+    `rows` sets FLAG_KEY_TABLE in the device guard word (check_guard_flags); either pair is skipped."""
+    _need_gpu(q, rows, row0, n_keys, tail_weight, q_index, kv_index, left, bias, out)
+    if q.dim() != 3 or rows.dim() != 2 or q.shape[2] != 128 or rows.shape[1] != 256 or q.stride(2) != 1 or rows.stride(1) != 1:
+        raise ValueError("pgca_pairs_ragged: q must be (n_q, Lq, 128) and rows (R, 256) with contiguous columns")
+    if rows.dtype != q.dtype:
+        raise ValueError("pgca_pairs_ragged: q is %s, rows is %s" % (q.dtype, rows.dtype))
+    for t in (q_index, kv_index):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != q_index.numel():
+            raise ValueError("pgca_pairs_ragged: q_index / kv_index must be contiguous int32 vectors of one length")
+    for t, dt, what in ((row0, torch.int64, "row0 int64"), (n_keys, torch.int32, "n_keys int32"), (tail_weight, torch.float32, "tail_weight float32")):
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() != row0.numel() or t.device != q.device:
+            raise ValueError("pgca_pairs_ragged: the key table is three contiguous vectors of one length on q's device "
+                             "(row0 int64, n_keys int32, tail_weight float32); %s is %s %s" % (what, t.dtype, tuple(t.shape)))
+    if int(key_tail_rows) < 0:
+        raise ValueError("pgca_pairs_ragged: key_tail_rows %d is negative" % int(key_tail_rows))
+    n_pairs, (n_q, Lq, E), n_kv = q_index.numel(), q.shape, row0.numel()
+    left_cols = 0
+    if left is not None:
+        if left.dim() != 3 or left.shape[:2] != q.shape[:2] or left.dtype != q.dtype or left.stride(2) != 1:
+            raise ValueError("pgca_pairs_ragged: left must be (n_q, Lq, cols) of q's dtype with contiguous columns")
+        left_cols = left.shape[2]
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != E or not bias.is_contiguous()):
+        raise ValueError("pgca_pairs_ragged: bias must be a contiguous float32 vector of %d" % E)
+    cols = left_cols + E
+    if out is None:
+        out = torch.empty((n_pairs, Lq, cols), dtype=q.dtype, device=q.device)
+    elif (out.dim() != 3 or out.dtype != q.dtype or out.device != q.device or out.shape[0] != n_pairs or out.shape[1] != Lq
+          or out.shape[2] < cols or out.stride(2) != 1 or out.stride(1) < cols or (n_pairs > 1 and out.stride(0) < (Lq - 1) * out.stride(1) + cols)):
+        raise ValueError("pgca_pairs_ragged: out must be a %s tensor of (%d, %d, >= %d) on q's device with contiguous columns and "
+                         "non-overlapping rows (got %s, strides %s)" % (q.dtype, n_pairs, Lq, cols, tuple(out.shape), out.stride()))
+    a = PgcaPairsRaggedArgs()
+    a.Q, a.K, a.V, a.left, a.out, a.bias = q.data_ptr(), rows.data_ptr(), rows.data_ptr() + E * rows.element_size(), _ptr(left), out.data_ptr(), _ptr(bias)
+    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
+    a.kv_row0, a.kv_keys, a.kv_tail_weight = row0.data_ptr(), n_keys.data_ptr(), tail_weight.data_ptr()
+    a.q_es, a.q_rs = q.stride(0), q.stride(1)
+    a.k_rs = a.v_rs = rows.stride(0)
+    if left is not None:
+        a.left_es, a.left_rs = left.stride(0), left.stride(1)
+    a.out_ps, a.out_rs = out.stride(0), out.stride(1)
+    a.kv_total_rows = rows.shape[0]
+    a.n_pairs, a.n_q, a.n_kv, a.Lq, a.head_dim, a.dtype = n_pairs, n_q, n_kv, Lq, E, _dt(q)
+    a.left_cols, a.out_col0 = left_cols, left_cols
+    a.scale = float(scale)
+    a.key_tail_rows = int(key_tail_rows)
+    check(_lib.lib().dl_pgca_pairs_ragged_fwd(C.byref(a), _stream()), "dl_pgca_pairs_ragged_fwd")
+    return out
+
+
 def dropout_apply(x2d: torch.Tensor, p: float, seed: int) -> torch.Tensor:
     y = torch.empty_like(x2d)
     rows, D = x2d.shape
@@ -951,7 +1005,10 @@ FLAG_TEXT = {_lib.FLAG_PROT_PERIOD: "a protein's residue codes / fill bits are n
              _lib.FLAG_PLAN_ROWS: "the ProteinCNN row tables were built with fewer rows than the batch's residue counts need "
                                   "(dl_protein_plan_build capacity)",
              _lib.FLAG_PAIR_INDEX: "a (protein, drug) pair of a screening launch names an entity outside the cached codes; the pair "
-                                   "was skipped (dl_pgca_pairs_fwd)"}
+                                   "was skipped (dl_pgca_pairs_fwd)",
+             _lib.FLAG_KEY_TABLE: "a drug's entry of a library screening launch's key table does not describe rows inside the row store "
+                                  "(negative first row, fewer keys than the tail, rows past the end, or a weight that is not a finite "
+                                  "value >= 1); the pair was skipped (dl_pgca_pairs_ragged_fwd)"}
 
 
 def guard_flags(device) -> torch.Tensor:

@@ -22,10 +22,18 @@ softmax (:290-314):  softmax(Q K^T) V W_o^T = softmax(Q K^T) (V W_o^T).  So
 
 model.score_codes (model/basic_model.py) runs the pair stage from these with one ops.pgca_pairs launch per branch.
 Codes record the compute dtype and the parameter epoch (functional.bump_param_epoch) they were built at.
+
+  DrugLibrary, per branch: the resident form of many DrugCodes of ANY layouts — one packed row store with a per-drug table
+      rows (R, 256)  row0 (D,) int64  n_keys (D,) int32  tail_weight (D,) fp32  bias (128,) fp32
+                               drug d owns rows row0[d] .. row0[d] + n_keys[d] - 1; each of its last 8 rows stands for
+                               tail_weight[d] identical keys.  A drug is trimmed to its own rows: roundup8(rows in front
+                               of its trailing run of padding rows) + 8 keys instead of the batch's block + 8 or 512.
+model.score_library runs the pair stage from it with one ops.pgca_pairs_ragged launch per branch.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence, Tuple
+import hashlib
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -152,3 +160,162 @@ class DrugCode(_Code):
                     raise ValueError("DrugCode.cat: branch %s has %s keys in full form" % (k, sorted({b.layout[0] for b in bs})))
             out[k] = DrugBranch(torch.cat([b.kv for b in bs]), bs[0].bias, bs[0].layout)
         return cls(out, c0.dtype, c0.epoch)
+
+
+LIB_TAIL_ROWS = 8                  # key_tail_rows of every library launch
+
+
+def fingerprint(model: torch.nn.Module, dtype: torch.dtype) -> str:
+    """sha1 over the model's state_dict (names and tensor bytes in key order, computed on the CPU) and the compute dtype: what
+    a saved library is valid for (the parameter epoch is a per-process counter and means nothing in a file)."""
+    h = hashlib.sha1()
+    for k, v in model.state_dict().items():
+        t = v.detach().cpu().contiguous().reshape(-1)
+        h.update(k.encode() + b"\0" + str(t.dtype).encode() + b"\0")
+        h.update(t.view(torch.uint8).numpy().tobytes())
+    h.update(str(dtype).encode())
+    return h.hexdigest()
+
+
+class LibraryBranch:
+    __slots__ = ("rows", "row0", "n_keys", "tail_weight", "bias")
+
+    def __init__(self, rows, row0, n_keys, tail_weight, bias):
+        self.rows, self.row0, self.n_keys, self.tail_weight, self.bias = rows, row0, n_keys, tail_weight, bias
+
+
+def _trim_branch(b: DrugBranch):
+    """(rows (R, 256), n_keys (D,) int64, tail_weight (D,) fp32) of one code's branch, every drug trimmed to its own rows.
+
+    Drug d's last row x is its padding row; rows equal to x BY VALUE (torch.eq: -0.0 == +0.0 — the GCN's in-block virtual
+    nodes pass through the aggregation product, which can turn one into the other; NaN != NaN, so such a drug is kept whole)
+    at the end of the drug are the trailing run.  lead = the rows in front of it rounded up to a multiple of 8; the code stood
+    for count = (Lk - t) + t * w keys (Lk without a tail); with count - lead a multiple of 8 and >= 16 the drug becomes
+    kv[:lead] followed by 8 copies of x, weight (count - lead) / 8.  Otherwise (and where the code's t tail rows are not all
+    equal to x) its rows are stored unchanged with the code's own weight.  Equal rows have equal scores and equal values, so
+    the softmax over lead + 8 * weight = count keys is the one over the code's keys."""
+    Lk, t, w = b.layout
+    T = LIB_TAIL_ROWS
+    if t not in (0, T):
+        raise ValueError("DrugLibrary: a code with %d tail rows (the library's kernel launches take %d or none)" % (t, T))
+    if Lk < T:
+        raise ValueError("DrugLibrary: a code of %d keys (at least %d are needed)" % (Lk, T))
+    kv = b.kv
+    D = kv.shape[0]
+    dev = kv.device
+    count = (Lk - t) + t * w if t else Lk
+    eq = (kv == kv[:, -1:, :]).all(dim=2)                                     # (D, Lk): row equals the drug's last row
+    pos = torch.arange(1, Lk + 1, device=dev)
+    front = (pos * (~eq)).amax(dim=1)                                         # rows in front of the trailing run of equal rows
+    lead = (front + 7) // 8 * 8
+    rest = count - lead
+    trim = (rest >= 2 * T) & (rest % T == 0)
+    if t:
+        trim &= eq[:, Lk - t:].all(dim=1)
+    n_keys = torch.where(trim, lead + T, torch.full_like(lead, Lk))
+    weight = torch.where(trim, rest // T, torch.full_like(lead, w if t else 1)).to(torch.float32)
+    start = torch.cumsum(n_keys, 0) - n_keys
+    drug = torch.repeat_interleave(torch.arange(D, device=dev), n_keys)      # (a host sync for the row count: a one-time build step)
+    r = torch.arange(drug.numel(), device=dev) - start[drug]
+    src = torch.where(trim[drug] & (r >= lead[drug]), torch.full_like(r, Lk - 1), r)
+    rows = kv.reshape(D * Lk, kv.shape[2]).index_select(0, drug * Lk + src)
+    return rows, n_keys, weight
+
+
+class DrugLibrary:
+    """A resident drug library: per branch a LibraryBranch (see the module text), plus the compute dtype, the parameter epoch
+    and — when built or loaded with the model — the parameter fingerprint that a saved file carries."""
+
+    def __init__(self, branches: Dict[str, LibraryBranch], dtype: torch.dtype, epoch: int, fingerprint_: Optional[str] = None):
+        self.branches, self.dtype, self.epoch, self.fingerprint = dict(branches), dtype, int(epoch), fingerprint_
+
+    # ---- building -------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_codes(cls, codes: Iterable[DrugCode], model: Optional[torch.nn.Module] = None) -> "DrugLibrary":
+        """The library of the drugs of `codes` (DrugCodes of any layouts, in order; an iterator is consumed code by code, so
+        that only the trimmed rows of earlier codes stay alive).  No code is expanded to its full key set.  Plain torch ops:
+        runs on CPU tensors too.  model: stamps the library with the fingerprint `save` needs."""
+        c0, parts = None, {}
+        for c in codes:
+            if c0 is None:
+                c0 = c
+            elif c.dtype != c0.dtype or c.epoch != c0.epoch or set(c.branches) != set(c0.branches):
+                raise ValueError("DrugLibrary: codes of different compute dtypes, parameter epochs or branches")
+            for k, b in c.branches.items():
+                parts.setdefault(k, []).append(_trim_branch(b) + (b.bias,))
+        if c0 is None:
+            raise ValueError("DrugLibrary.from_codes: no codes")
+        branches = {}
+        for k, ps in parts.items():
+            n_keys = torch.cat([p[1] for p in ps])
+            branches[k] = LibraryBranch(torch.cat([p[0] for p in ps]), torch.cumsum(n_keys, 0) - n_keys, n_keys.to(torch.int32),
+                                        torch.cat([p[2] for p in ps]), ps[0][3])
+        return cls(branches, c0.dtype, c0.epoch, None if model is None else fingerprint(model, c0.dtype))
+
+    def append(self, dcode: DrugCode) -> "DrugLibrary":
+        """Adds the drugs of one more code behind the library's (in place; returns self).  Copies the row store once: build a
+        large library with from_codes over all its codes."""
+        if dcode.dtype != self.dtype or dcode.epoch != self.epoch or set(dcode.branches) != set(self.branches):
+            raise ValueError("DrugLibrary.append: the code's compute dtype, parameter epoch or branches differ from the library's")
+        for k, b in dcode.branches.items():
+            rows, n_keys, weight = _trim_branch(b)
+            lb = self.branches[k]
+            row0 = lb.rows.shape[0] + torch.cumsum(n_keys, 0) - n_keys
+            self.branches[k] = LibraryBranch(torch.cat([lb.rows, rows]), torch.cat([lb.row0, row0]), torch.cat([lb.n_keys, n_keys.to(torch.int32)]),
+                                             torch.cat([lb.tail_weight, weight]), lb.bias)
+        return self
+
+    # ---- what it holds --------------------------------------------------------------------------------------------------
+    @property
+    def n(self) -> int:
+        return int(next(iter(self.branches.values())).n_keys.numel())
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for b in self.branches.values()
+                   for t in (b.rows, b.row0, b.n_keys, b.tail_weight, b.bias) if t is not None)
+
+    def keys(self, branch: str = "v") -> torch.Tensor:
+        """The stored key count of every drug, (D,) int32."""
+        return self.branches[branch].n_keys
+
+    def expand(self, branch: str, i: int) -> torch.Tensor:
+        """Drug i's code over its full key set (lead + 8 * weight rows, 512 on the model's path) in ExpandTailFn's order: tail row
+        j at rows lead + m * 8 + j (m < weight).  For tests and debugging."""
+        b = self.branches[branch]
+        r0, n, w = int(b.row0[i]), int(b.n_keys[i]), int(b.tail_weight[i])
+        T = LIB_TAIL_ROWS
+        idx = torch.cat([torch.arange(n - T), n - T + torch.arange(T * w) % T]).to(b.rows.device)
+        return b.rows[r0:r0 + n].index_select(0, idx)
+
+    # ---- persistence ----------------------------------------------------------------------------------------------------
+    def save(self, path) -> None:
+        """One torch.save of a dict of tensors and plain scalars (readable with weights_only=True)."""
+        if self.fingerprint is None:
+            raise RuntimeError("DrugLibrary.save: the library has no parameter fingerprint (build it with from_codes(codes, model) "
+                               "or Trainer.build_library)")
+        blob = {"format": 1, "dtype": str(self.dtype).split(".")[1], "fingerprint": self.fingerprint, "branches": sorted(self.branches)}
+        for k, b in self.branches.items():
+            for f in LibraryBranch.__slots__:
+                t = getattr(b, f)
+                if t is not None:
+                    blob["%s.%s" % (k, f)] = t.detach().cpu()
+        torch.save(blob, path)
+
+    @classmethod
+    def load(cls, path, model: torch.nn.Module, device=None) -> "DrugLibrary":
+        """Reads a saved library for `model`: the file's fingerprint must be that of the model's parameters now (RuntimeError
+        otherwise); the library is stamped with the current parameter epoch."""
+        blob = torch.load(path, map_location="cpu", weights_only=True)
+        if blob.get("format") != 1 or blob.get("dtype") not in ("float32", "bfloat16"):
+            raise RuntimeError("DrugLibrary.load: %s is not a saved drug library" % (path,))
+        dtype = getattr(torch, blob["dtype"])
+        now = fingerprint(model, dtype)
+        if blob["fingerprint"] != now:
+            raise RuntimeError("DrugLibrary.load: the library was built with other parameters or another compute dtype "
+                               "(fingerprint %s, the model's is %s); build it again" % (blob["fingerprint"], now))
+        branches = {}
+        for k in blob["branches"]:
+            ts = [blob.get("%s.%s" % (k, f)) for f in LibraryBranch.__slots__]
+            branches[k] = LibraryBranch(*[t if t is None or device is None else t.to(device) for t in ts])
+        return cls(branches, dtype, param_epoch(), now)

@@ -980,6 +980,72 @@ class Trainer:
         self.check_device_flags()
         return out
 
+    @torch.no_grad()
+    def build_library(self, drug_batches, hints=None):
+        """A resident screening.DrugLibrary of every drug of `drug_batches` (yields (feat_d, llm_d) as `screen` takes them):
+        encode_drugs per batch, every drug trimmed to its own keys whatever layout its batch was encoded in.  hints: None, one
+        BatchHints for every batch, or a sequence with one entry (BatchHints or None) per batch."""
+        from .screening import DrugLibrary
+        self.model.eval()
+        per_batch = hints is not None and not hasattr(hints, "drug_tokens")
+        hs = iter(hints) if per_batch else None
+
+        def codes():
+            for feat_d, llm_d in drug_batches:
+                yield self.model.encode_drugs(feat_d, llm_d, next(hs) if per_batch else hints)
+        lib = DrugLibrary.from_codes(codes(), self.model)
+        self.check_device_flags()
+        return lib
+
+    @torch.no_grad()
+    def screen_library(self, protein_batches, lib, pair_batch: int = 256, top_k: Optional[int] = None):
+        """`screen` against a resident drug library: the library stays where it is, the protein batches are streamed — encode
+        one, score it against every drug in chunks of pair_batch pairs (drug-major, as in `screen`), drop its code.
+        top_k=None: the (P, D) fp32 probabilities of `screen`.  top_k=k: (values (P, k), indices (P, k) int64), the k most
+        probable drugs per protein in descending order, merged chunk by chunk with torch.topk on the device: memory is
+        O(P k + pair_batch) whatever the library size."""
+        if pair_batch < 1:
+            raise ValueError("screen_library: pair_batch must be positive")
+        D = lib.n
+        if top_k is not None and not 1 <= int(top_k) <= D:
+            raise ValueError("screen_library: top_k %s not in [1, %d]" % (top_k, D))
+        self.model.eval()
+        rows, vals, idxs = [], [], []
+        for feat_p, llm_p in protein_batches:
+            pcode = self.model.encode_proteins(feat_p, llm_p)
+            Pn = pcode.n
+            d_step = max(1, pair_batch // Pn)                  # whole drugs per chunk: a chunk is a (drugs, Pn) block
+            best_v = best_i = None
+            cols = []
+            for d0 in range(0, D, d_step):
+                d1 = min(D, d0 + d_step)
+                di = torch.arange(d0, d1).repeat_interleave(Pn)     # drug-major
+                pi = torch.arange(Pn).repeat(d1 - d0)
+                score = self.model.score_library(pcode, lib, pi, di)
+                prob = torch.sigmoid(score).squeeze(1) if self.n_class == 1 else torch.softmax(score, dim=1)[:, 1]
+                prob = prob.view(d1 - d0, Pn).t()                   # (Pn, drugs d0 .. d1 - 1)
+                if top_k is None:
+                    cols.append(prob)
+                    continue
+                ids = torch.arange(d0, d1, device=prob.device).expand(Pn, -1)
+                if best_v is not None:
+                    prob, ids = torch.cat([best_v, prob], dim=1), torch.cat([best_i, ids], dim=1)
+                best_v, sel = torch.topk(prob, min(int(top_k), prob.shape[1]), dim=1)
+                best_i = torch.gather(ids, 1, sel)
+            if top_k is None:
+                rows.append(torch.cat(cols, dim=1))
+            else:
+                vals.append(best_v)
+                idxs.append(best_i)
+            del pcode
+        self.check_device_flags()
+        if top_k is None:
+            return torch.cat(rows).contiguous() if rows else torch.zeros((0, D), dtype=torch.float32, device=self.device)
+        if not vals:
+            return (torch.zeros((0, int(top_k)), dtype=torch.float32, device=self.device),
+                    torch.zeros((0, int(top_k)), dtype=torch.int64, device=self.device))
+        return torch.cat(vals).contiguous(), torch.cat(idxs).contiguous()
+
     def evaluate(self, batches) -> Dict[str, float]:
         """Metrics over the union of all ranks' samples (the reference's torchmetrics objects gather their states at
         epoch end, trainer.py:262-292; its logged loss is `sync_dist=True`): ranks may hold different numbers of samples."""

@@ -381,6 +381,52 @@ typedef struct {
 } dl_pgca_pairs_args;
 int dl_pgca_pairs_fwd(const dl_pgca_pairs_args* a, dl_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Pair-indexed PGCA attention core over a packed per-drug row store (forward only): the resident
+ * drug library of the screening path.  dl_pgca_pairs_fwd takes one Lk and one key_tail_weight for the
+ * whole launch; here every drug has its own key count and multiplicity, read from a device table.
+ *
+ * K and V point into one row store of kv_total_rows rows ([K | V'] with row strides k_rs, v_rs).
+ * Drug d < n_kv owns the segment of Lk_d = kv_keys[d] rows that starts at row kv_row0[d]; each of the
+ * segment's last key_tail_rows rows stands for w_d = kv_tail_weight[d] identical keys (w_d = 1: ordinary
+ * keys).  key_tail_rows is launch-wide.
+ *
+ * For pair n < n_pairs with p = q_index[n], d = kv_index[n] (int32, device memory):
+ *   S = scale * Q[p] K_d^T  (+ log w_d on the last key_tail_rows keys of the segment)
+ *   O = softmax(S) V_d  (+ bias[c] in column c, fp32, if bias is given)
+ *   out (n, r, out_col0 + c) = O[r][c]         c < head_dim, r < Lq
+ *   out (n, r, c)            = left (p, r, c)  c < left_cols (bitwise copy; only with left != NULL)
+ * Addressing (element strides, all tensors dtype `dtype`, columns contiguous):
+ *   q    (e, r, :) = Q + e*q_es + r*q_rs          e < n_q
+ *   K_d  (j, :)    = K + (kv_row0[d] + j)*k_rs     j < Lk_d     (V_d: V, v_rs)
+ *   left (e, r, :) = left + e*left_es + r*left_rs  e < n_q
+ *   out  (n, r, :) = out + n*out_ps + r*out_rs
+ * kv_row0 (int64), kv_keys (int32), kv_tail_weight (float): device vectors of n_kv entries.
+ * Nothing is written outside the addressed columns of the addressed rows; no row outside a pair's
+ * segment is read for it.
+ * The table lives on the device, so the kernel checks it: a pair is skipped — nothing is read through
+ * its table entry, nothing is written for it — when
+ *   its index is outside [0, n_q) or [0, n_kv)                        -> DL_FLAG_PAIR_INDEX is OR-ed into *flags
+ *   kv_row0[d] < 0, kv_keys[d] < max(1, key_tail_rows),
+ *   kv_row0[d] + kv_keys[d] > kv_total_rows, or kv_tail_weight[d] is
+ *   not a finite value >= 1                                            -> DL_FLAG_KEY_TABLE
+ * (flags may be NULL).  One head, head_dim == 128 (else DL_ERR_UNSUPPORTED); Lq arbitrary; Q / K / V / left / out /
+ * bias 16-byte aligned, strides multiples of 16 bytes; kv_row0 8-byte, the other index vectors 4-byte aligned;
+ * left_cols and out_col0 multiples of 8 elements, left_cols <= out_col0, out_rs >= out_col0 + 128;
+ * key_tail_rows >= 0, kv_total_rows >= 0.  n_pairs == 0: DL_OK, nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* Q; const void* K; const void* V; const void* left; void* out; const float* bias;
+  const int32_t* q_index; const int32_t* kv_index;
+  const int64_t* kv_row0; const int32_t* kv_keys; const float* kv_tail_weight; uint32_t* flags;
+  int64_t q_es, q_rs, k_rs, v_rs, left_es, left_rs, out_ps, out_rs, kv_total_rows;
+  int32_t n_pairs, n_q, n_kv, Lq, head_dim, dtype;
+  int32_t left_cols, out_col0;
+  float scale;
+  int32_t key_tail_rows;
+} dl_pgca_pairs_ragged_args;
+int dl_pgca_pairs_ragged_fwd(const dl_pgca_pairs_ragged_args* a, dl_stream s);
+
 
 /* ------------------------------------------------------------------------------------------
  * MHLA token gate (MultiHeadLinearAttention.forward, model/PMMA/encoder.py:127-140):
@@ -467,7 +513,8 @@ int dl_embed_pad(const int64_t* ids, const void* weight, const void* fill, void*
 /* Device-side guard flags (sticky bits OR-ed into a caller-owned uint32 word; the trainer polls it):
  * the compact forms below are only valid for inputs with the padding structure of the reference's collate. */
 enum { DL_FLAG_PROT_PERIOD = 1, DL_FLAG_DRUG_TOKEN_PAD = 2, DL_FLAG_GCN_NODE_PAD = 4, DL_FLAG_PLAN_ROWS = 8,
-       DL_FLAG_PAIR_INDEX = 16 /* dl_pgca_pairs_fwd: a pair's entity index is out of range (the pair was skipped) */ };
+       DL_FLAG_PAIR_INDEX = 16 /* dl_pgca_pairs_fwd: a pair's entity index is out of range (the pair was skipped) */,
+       DL_FLAG_KEY_TABLE = 32 /* dl_pgca_pairs_ragged_fwd: a drug's key table entry is malformed (the pair was skipped) */ };
 /* ProteinCNN head on distinct rows (round 4; model/basic_model.py:168-171 over a sequence tiled by utils.py:392-412):
  * out[r][:D] = weight[ids[src[r]]], out[r][D] = fill[src[r]] for src[r] >= 0 (a flat index into ids / fill [B * L]), a zero
  * row for src[r] < 0.  weight padded to [V][D + 1] as for dl_embed_pad.  With `period` [B] given the same launch checks
