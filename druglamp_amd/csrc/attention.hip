@@ -18,10 +18,6 @@
 namespace {
 using namespace dltile;
 
-// v_exp_f32 without libm's denormal-range fix-up (arguments here are <= 0 and results below 2^-126 may flush);
-// exp2(-inf) = 0 as the online softmax needs
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
 struct AttnP {
   const char *Q, *K, *V, *O, *dO;
   char *Out, *dQ, *dK, *dV;
@@ -52,26 +48,6 @@ __device__ __forceinline__ void add_tail_bias_t(f32x4 (&s)[QT][NKT], int k0, int
       }
 }
 
-__device__ __attribute__((aligned(16))) const uint32_t attn_zero_page[4] = {0u, 0u, 0u, 0u};
-
-// LDS-DMA of `total_rows` (a multiple of 64) rows of head_dim elements into an ATile image: source-side XOR
-// swizzle, rows >= valid_rows read a zero page.  NT threads; completes at the next __syncthreads().
-template <typename T, int HD, int NT>
-__device__ __forceinline__ void dma_rows(char* lds, const T* base, int64_t row_stride, int valid_rows, int total_rows) {
-  using TL = ATile<T, HD>;
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int nchunks = total_rows * TL::CPR;
-  const char* zero = reinterpret_cast<const char*>(attn_zero_page);
-  for (int c0 = 0; c0 < nchunks; c0 += NT) {
-    const int c = c0 + tid;
-    const int row = c / TL::CPR, ch = (c % TL::CPR) ^ TL::swz(row);
-    const char* src = (c < nchunks && row < valid_rows) ? reinterpret_cast<const char*>(base + (int64_t)row * row_stride + ch * TL::EPC) : zero;
-    const uint32_t off = __builtin_amdgcn_readfirstlane((uint32_t)((c0 + wave * 64) * 16));
-    if (c0 + wave * 64 < nchunks)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(lds + off), 16, 0, 0);
-  }
-}
 // sum_d a[d] * b[d] over the 8 bf16 of one fragment
 __device__ __forceinline__ float dot8_bf16(u32x4 a, u32x4 b) {
   float s = 0.f;
@@ -261,7 +237,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_res_kernel(const AttnP p)
   const int nt = (p.Lk + KVB - 1) / KVB;
   {
     const int nchunks = nt * KVB * TL::CPR;          // whole key tiles; rows >= Lk are zero
-    const char* zero = reinterpret_cast<const char*>(attn_zero_page);
+    const char* zero = reinterpret_cast<const char*>(zero_page);
     for (int c0 = 0; c0 < nchunks; c0 += NT) {
       const int c = c0 + tid;
       const int row = c / TL::CPR, ch = (c % TL::CPR) ^ TL::swz(row);
@@ -629,7 +605,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq_ring_kernel(const 
     const int64_t statbase = (((int64_t)seg * p.P + pa) * p.H + h) * p.Lq;
     const int nt = (p.Lk + KVB - 1) / KVB;
     auto issue = [&](int t, int buf) {
-      const char* zero = reinterpret_cast<const char*>(attn_zero_page);
+      const char* zero = reinterpret_cast<const char*>(zero_page);
       const uint32_t sb = smem_lds + (uint32_t)buf * STAGE;
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
@@ -930,7 +906,7 @@ __global__ __launch_bounds__(ATT_THREADS, 1) void attn_bwd_dkv_ring_kernel(const
     const int64_t statbase = (((int64_t)seg * p.P + pa) * p.H + h) * p.Lq;
     // block qb -> stage qb & 1: Q / dO rows by DMA, LSE / Delta rows by the first 64 threads
     auto issue = [&](int qb, int buf) {
-      const char* zero = reinterpret_cast<const char*>(attn_zero_page);
+      const char* zero = reinterpret_cast<const char*>(zero_page);
       const uint32_t sb = smem_lds + (uint32_t)buf * STAGE;
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
@@ -1079,7 +1055,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_fused_kernel(const AttnP p) {
   const int nblk = (p.Lq + QBLK - 1) / QBLK;
   const int G = npass * nblk;                              // blocks of the whole workgroup, in order
   const uint32_t smem_base = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem;   // LDS byte address (for M0)
-  const char* zero = reinterpret_cast<const char*>(attn_zero_page);
+  const char* zero = reinterpret_cast<const char*>(zero_page);
 
   // ---- ring DMA, one block per call, in block order: wave w moves rows 8 (w & 3) .. + 7 of the Q (w < 4) or dO (w >= 4) tile,
   // waves 0-3 also the same rows of the O tile, wave 4 the 32 LSE values: two instructions for waves 0-4, one for waves 5-7.

@@ -16,9 +16,6 @@
 namespace {
 using namespace dltile;
 
-// v_exp_f32 without libm's denormal-range fix-up (arguments here are <= ~0 and results below 2^-126 may flush)
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
 struct ProbsP {
   const char *Q, *K;
   const float* LSE;      // statistics the map kernel reads
@@ -34,28 +31,6 @@ struct ProbsP {
   int expand;
   int vec;               // out and out_ld allow 16-byte stores
 };
-
-__device__ __attribute__((aligned(16))) const uint32_t probs_zero_page[4] = {0u, 0u, 0u, 0u};
-
-// LDS-DMA of `total_rows` (a multiple of 64) rows of head_dim elements into an ATile image: source-side XOR
-// swizzle, rows >= valid_rows read a zero page.  NT threads; complete for the workgroup after vm_wait<0>() + __syncthreads().
-// (attention.hip's loader: that file keeps it in its anonymous namespace)
-template <typename T, int HD, int NT>
-__device__ __forceinline__ void dma_rows(char* lds, const T* base, int64_t row_stride, int valid_rows, int total_rows) {
-  using TL = ATile<T, HD>;
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int nchunks = total_rows * TL::CPR;
-  const char* zero = reinterpret_cast<const char*>(probs_zero_page);
-  for (int c0 = 0; c0 < nchunks; c0 += NT) {
-    const int c = c0 + tid;
-    const int row = c / TL::CPR, ch = (c % TL::CPR) ^ TL::swz(row);
-    const char* src = (c < nchunks && row < valid_rows) ? reinterpret_cast<const char*>(base + (int64_t)row * row_stride + ch * TL::EPC) : zero;
-    const uint32_t off = __builtin_amdgcn_readfirstlane((uint32_t)((c0 + wave * 64) * 16));
-    if (c0 + wave * 64 < nchunks)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(lds + off), 16, 0, 0);
-  }
-}
 
 constexpr int KVB = 64, NKT = KVB / 16;   // keys per LDS tile, 16-key score tiles in it
 

@@ -1,73 +1,96 @@
-// pgca_pairs.hip — pair-indexed PGCA attention core of the screening path (forward only).
-// See include/druglamp_hip.h (dl_pgca_pairs_fwd) for the addressing.
+// pgca_pairs.hip — pair-indexed PGCA attention core of the screening path (forward only), over dense per-entity codes
+// (dl_pgca_pairs_fwd) or over a packed per-drug row store (dl_pgca_pairs_ragged_fwd: the resident drug library).
+// See include/druglamp_hip.h for the addressing of both.
 //
-//   Pair n reads its queries from entity q_index[n] of Q and its keys / values from entity kv_index[n] of K / V: the
-//   operands are the cached per-entity codes (druglamp_amd/screening.py), nothing is gathered per pair.
+//   Pair n reads its queries from entity q_index[n] of Q and its keys / values from the segment of K / V that entity
+//   kv_index[n] owns: the operands are the cached per-entity codes (druglamp_amd/screening.py), nothing is gathered per pair.
+//   Where that segment lies is the one thing the two entry points differ in, and the kernel takes it from its `Keys` type:
+//     DenseKeys  : entity d of K / V, k_es / v_es elements apart; Lk, the tail rows and their weight are launch-wide.
+//     RaggedKeys : rows kv_row0[d] .. kv_row0[d] + kv_keys[d] - 1 of one packed [K | V'] row store, whose last key_tail_rows
+//                  rows stand for kv_tail_weight[d] identical keys each (DrugLibrary); the table entry is read at the top of
+//                  the workgroup (scalar loads: the entry's index is a scalar load itself).  The workgroups of a short drug
+//                  run fewer tiles; rows >= Lk of the last tile read the zero page, never the next drug's rows.
 //
 //   pgca_pairs_kernel : one workgroup owns 64 * QT query rows of one pair; a wave owns 16 * QT of them.  The arithmetic is
-//                       attention.hip's streamed forward: 64-key tiles of K and V pass through two LDS buffers by LDS-DMA,
-//                       scores in the transposed layout (S^T = K Q^T, lane (il, g) holds keys 4g + r of query il), online
-//                       maximum / sum, O^T += V^T P^T with P^T straight from the accumulators.  The epilogue adds the fp32
-//                       bias and stores O at columns out_col0.. of the pair's rows; the same workgroup copies its rows of
-//                       `left` (the protein sites) to columns 0..left_cols-1, so that `out` is the [sites | guided] concat
-//                       the MHLA block takes.  Workgroups of one pair are consecutive in the grid, and so are the pairs of a
-//                       caller that orders them by key entity: they find K | V in L2.
-//                       A pair whose index is out of range returns before it reads or writes anything (the test is uniform
-//                       for the workgroup: both indices are scalar loads) and ORs DL_FLAG_PAIR_INDEX into the guard word.
+//                       attention.hip's streamed forward (the three tile steps of tiles.cuh): 64-key tiles of K and V pass
+//                       through two LDS buffers by LDS-DMA, scores in the transposed layout (S^T = K Q^T, lane (il, g) holds
+//                       keys 4g + r of query il), online maximum / sum, O^T += V^T P^T with P^T straight from the
+//                       accumulators.  The epilogue adds the fp32 bias and stores O at columns out_col0.. of the pair's rows;
+//                       the same workgroup copies its rows of `left` (the protein sites) to columns 0..left_cols-1, so that
+//                       `out` is the [sites | guided] concat the MHLA block takes.  The grid is n_pairs x ceil(Lq / (64 QT)).
+//                       Workgroups of one pair are consecutive in the grid, and so are the pairs of a caller that orders
+//                       them by key entity: they find K | V in L2.
+//                       A pair whose index is out of range (DL_FLAG_PAIR_INDEX), or whose drug's table entry does not
+//                       describe rows inside the store (DL_FLAG_KEY_TABLE), returns before it reads anything through the
+//                       entry or writes anything; both tests are uniform for the workgroup.
 #include "tiles.cuh"
 
 namespace {
 using namespace dltile;
 
-// v_exp_f32 without libm's denormal-range fix-up (arguments here are <= 0 and results below 2^-126 may flush);
-// exp2(-inf) = 0 as the online softmax needs
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-struct PairsP {
+// the part of the launch that does not depend on where a pair's keys lie
+struct PairsCommon {
   const char *Q, *K, *V, *left;
   char* out;
   const float* bias;
   const int32_t *qi, *ki;
   uint32_t* flags;
-  int64_t q_es, q_rs, k_es, k_rs, v_es, v_rs, left_es, left_rs, out_ps, out_rs;
-  int n_q, n_kv, Lq, Lk, bps;      // bps: workgroups per pair
+  int64_t q_es, q_rs, k_rs, v_rs, left_es, left_rs, out_ps, out_rs;
+  int n_q, n_kv, Lq, bps;          // bps: workgroups per pair
   int left_chunks;                 // 16-byte chunks of a row of `left` (0: no copy)
   int out_col0;
   float scale;
+};
+template <typename Keys> struct PairsP : PairsCommon {
+  Keys keys;
+};
+
+// the keys / values of one pair, as Keys::locate() finds them
+struct KeySeg {
+  int64_t k_off, v_off;            // elements from K / V to the segment's first row
+  int Lk;
   int tail_start;                  // Lk - key_tail_rows (== Lk: no key multiplicities)
   float tail_bias;                 // log(w) / scale, added to the UNSCALED score of a tail key (as attention.hip)
 };
 
-__device__ __attribute__((aligned(16))) const uint32_t pairs_zero_page[4] = {0u, 0u, 0u, 0u};
-
-// LDS-DMA of `total_rows` (a multiple of 64) rows of head_dim elements into an ATile image: source-side XOR
-// swizzle, rows >= valid_rows read a zero page.  NT threads; complete for the workgroup after vm_wait<0>() + __syncthreads().
-// (attention.hip's loader: that file keeps it in its anonymous namespace)
-template <typename T, int HD, int NT>
-__device__ __forceinline__ void dma_rows(char* lds, const T* base, int64_t row_stride, int valid_rows, int total_rows) {
-  using TL = ATile<T, HD>;
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int nchunks = total_rows * TL::CPR;
-  const char* zero = reinterpret_cast<const char*>(pairs_zero_page);
-  for (int c0 = 0; c0 < nchunks; c0 += NT) {
-    const int c = c0 + tid;
-    const int row = c / TL::CPR, ch = (c % TL::CPR) ^ TL::swz(row);
-    const char* src = (c < nchunks && row < valid_rows) ? reinterpret_cast<const char*>(base + (int64_t)row * row_stride + ch * TL::EPC) : zero;
-    const uint32_t off = __builtin_amdgcn_readfirstlane((uint32_t)((c0 + wave * 64) * 16));
-    if (c0 + wave * 64 < nchunks)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(lds + off), 16, 0, 0);
+struct DenseKeys {
+  int64_t k_es, v_es;
+  int Lk, tail_start;
+  float tail_bias;
+  __device__ __forceinline__ uint32_t locate(int di, int64_t, int64_t, float, KeySeg& s) const {
+    s.k_off = (int64_t)di * k_es;
+    s.v_off = (int64_t)di * v_es;
+    s.Lk = Lk; s.tail_start = tail_start; s.tail_bias = tail_bias;
+    return 0;
   }
-}
+};
+
+struct RaggedKeys {
+  const int64_t* row0;             // per drug: first row of its segment of the row store
+  const int32_t* keys;             //           rows of the segment (Lk_d)
+  const float* tailw;              //           multiplicity of each of the segment's last tail_rows rows
+  int64_t total_rows;
+  int tail_rows;                   // launch-wide key_tail_rows (0: no key multiplicities)
+  // an entry that does not describe rows inside the store is not used
+  __device__ __forceinline__ uint32_t locate(int di, int64_t k_rs, int64_t v_rs, float scale, KeySeg& s) const {
+    const int64_t r0 = row0[di];
+    const int Lk = keys[di];
+    const float tw = tailw[di];
+    if (r0 < 0 || Lk < max(1, tail_rows) || r0 > total_rows - (int64_t)Lk || !(tw >= 1.f && tw < INFINITY)) return DL_FLAG_KEY_TABLE;
+    s.k_off = r0 * k_rs;
+    s.v_off = r0 * v_rs;
+    s.Lk = Lk; s.tail_start = Lk - tail_rows; s.tail_bias = logf(tw) / scale;
+    return 0;
+  }
+};
 
 constexpr int KVB = 64;            // keys per streamed tile
 
 // LDS: two (K tile, V tile) pairs = 64 KB in bf16 (two workgroups per CU), 128 KB in fp32 (one: the parity dtype)
-template <typename T, int HD, int QT>
-__global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP p) {
+template <typename T, int HD, int QT, typename Keys>
+__global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP<Keys> p) {
   using TL = ATile<T, HD>;
-  constexpr int KF = Mma<T>::KF, NKF = HD / KF, NDT = HD / 16, CT = KF / 16;
-  constexpr int NKT = KVB / 16, NKP = KVB / KF;
+  constexpr int NKF = HD / Mma<T>::KF, NDT = HD / 16, NKT = KVB / 16;
   constexpr int QB = 4 * QT * 16;
   constexpr int BUF = 2 * KVB * TL::RB;                 // one (K tile, V tile) pair
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
@@ -75,13 +98,21 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, il = lane & 15, g = lane >> 4;
   const int n = blockIdx.x / p.bps, qb = blockIdx.x % p.bps;
   const int pi = p.qi[n], di = p.ki[n];
-  if ((unsigned)pi >= (unsigned)p.n_q || (unsigned)di >= (unsigned)p.n_kv) {     // the same for the whole workgroup
-    if (p.flags && qb == 0 && threadIdx.x == 0) atomicOr(p.flags, (uint32_t)DL_FLAG_PAIR_INDEX);
+  // Both guards are uniform for the workgroup: the indices and what locate() reads are scalar loads (the keys' entry is read
+  // only through an index in range; all of them in front of the one atomic, so that nothing the compiler must treat as a
+  // store precedes them).
+  KeySeg ks = {};
+  const bool in_range = (unsigned)pi < (unsigned)p.n_q && (unsigned)di < (unsigned)p.n_kv;
+  const uint32_t bad = in_range ? p.keys.locate(di, p.k_rs, p.v_rs, p.scale, ks) : (uint32_t)DL_FLAG_PAIR_INDEX;
+  if (bad) {                                            // the pair is skipped: nothing read through the entry, nothing written
+    if (p.flags && qb == 0 && threadIdx.x == 0) atomicOr(p.flags, bad);
     return;
   }
+  const int Lk = ks.Lk, tail_start = ks.tail_start;
+  const float tail_bias = ks.tail_bias;
   const T* Qb = reinterpret_cast<const T*>(p.Q) + (int64_t)pi * p.q_es;
-  const T* Kb = reinterpret_cast<const T*>(p.K) + (int64_t)di * p.k_es;
-  const T* Vb = reinterpret_cast<const T*>(p.V) + (int64_t)di * p.v_es;
+  const T* Kb = reinterpret_cast<const T*>(p.K) + ks.k_off;
+  const T* Vb = reinterpret_cast<const T*>(p.V) + ks.v_off;
   T* Ob = reinterpret_cast<T*>(p.out) + (int64_t)n * p.out_ps;
 
   const int qw0 = qb * QB + wave * QT * 16;
@@ -103,11 +134,11 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP
   for (int qt = 0; qt < QT; ++qt) { m_run[qt] = -INFINITY; l_run[qt] = 0.f; }
   const float c = p.scale * LOG2E;
 
-  const int nt = (p.Lk + KVB - 1) / KVB;
+  const int nt = (Lk + KVB - 1) / KVB;
   auto stage = [&](int t, int buf) {
     char* b = smem + buf * BUF;
-    dma_rows<T, HD, ATT_THREADS>(b, Kb + (int64_t)t * KVB * p.k_rs, p.k_rs, p.Lk - t * KVB, KVB);
-    dma_rows<T, HD, ATT_THREADS>(b + KVB * TL::RB, Vb + (int64_t)t * KVB * p.v_rs, p.v_rs, p.Lk - t * KVB, KVB);
+    dma_rows<T, HD, ATT_THREADS>(b, Kb + (int64_t)t * KVB * p.k_rs, p.k_rs, Lk - t * KVB, KVB);
+    dma_rows<T, HD, ATT_THREADS>(b + KVB * TL::RB, Vb + (int64_t)t * KVB * p.v_rs, p.v_rs, Lk - t * KVB, KVB);
   };
   stage(0, 0);
 
@@ -130,21 +161,10 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP
     if (t + 1 < nt) stage(t + 1, (t + 1) & 1);
     const char* Ks = smem + (t & 1) * BUF;
     const char* Vs = Ks + KVB * TL::RB;
-    // ---- S^T = K Q^T ----
     f32x4 s[QT][NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) s[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kf = 0; kf < NKF; ++kf) {
-        const u32x4 ka = frag_kc<T, HD>(Ks, kt * 16, kf, il, g);
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) s[qt][kt] = Mma<T>::mma(ka, qf[qt][kf], s[qt][kt]);
-      }
-    }
+    fwd_scores<T, HD>(Ks, qf, s, il, g);                // S^T = K Q^T
     // ---- key multiplicities, key masking (tiles in front of both skip this through a uniform branch) ----
-    if (k0 + KVB > p.tail_start || k0 + KVB > p.Lk) {
+    if (k0 + KVB > tail_start || k0 + KVB > Lk) {
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
@@ -152,50 +172,13 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP
           const int key = k0 + kt * 16 + 4 * g + r;
 #pragma unroll
           for (int qt = 0; qt < QT; ++qt) {
-            if (key >= p.tail_start) s[qt][kt][r] += p.tail_bias;
-            if (key >= p.Lk) s[qt][kt][r] = -INFINITY;
+            if (key >= tail_start) s[qt][kt][r] += tail_bias;
+            if (key >= Lk) s[qt][kt][r] = -INFINITY;
           }
         }
     }
-    // ---- online softmax (per q = il; replicated over g) ----
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[qt][kt][r]);
-      mx = group4_max(mx);
-      const float m_new = fmaxf(m_run[qt], mx);
-      const float alpha = fast_exp2((m_run[qt] - m_new) * c);
-      const float mc = m_new * c;
-      float rs = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float e = fast_exp2(s[qt][kt][r] * c - mc);
-          s[qt][kt][r] = e;
-          rs += e;
-        }
-      l_run[qt] = l_run[qt] * alpha + rs;   // per-lane partial (own keys); reduced at the end
-      m_run[qt] = m_new;
-#pragma unroll
-      for (int d = 0; d < NDT; ++d) o[d][qt] *= alpha;
-    }
-    // ---- O^T += V^T P^T ----
-#pragma unroll
-    for (int kp = 0; kp < NKP; ++kp) {
-      u32x4 pb[QT];
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) pb[qt] = frag_from_acc<T>(&s[qt][kp * CT]);
-#pragma unroll
-      for (int d = 0; d < NDT; ++d) {
-        const u32x4 va = frag_tr<T, HD>(Vs, kp * KF, d * 16, il, g);
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) o[d][qt] = Mma<T>::mma(va, pb[qt], o[d][qt]);
-      }
-    }
+    fwd_softmax(s, m_run, l_run, o, c);                 // online maximum / sum, rescale of o
+    fwd_accumulate<T, HD>(Vs, s, o, il, g);             // O^T += V^T P^T
     // (no barrier here: the one at the top of the next iteration is what separates this tile's reads from the DMA that
     //  refills its buffer two iterations later)
   }
@@ -219,27 +202,23 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP
 
 template <typename T> constexpr int pairs_qt() { return sizeof(T) == 2 ? 2 : 1; }
 
-template <typename T>
-void launch_pairs(PairsP& p, int n_pairs, hipStream_t s) {
-  constexpr int QT = pairs_qt<T>();
-  hipLaunchKernelGGL((pgca_pairs_kernel<T, 128, QT>), dim3((uint32_t)n_pairs * (uint32_t)p.bps), dim3(ATT_THREADS), 0, s, p);
+template <typename Keys>
+void launch_pairs(int dtype, const PairsP<Keys>& p, int n_pairs, hipStream_t s) {
+  const dim3 grid((uint32_t)n_pairs * (uint32_t)p.bps);
+  if (dtype == DL_BF16) hipLaunchKernelGGL((pgca_pairs_kernel<bf16_t, 128, pairs_qt<bf16_t>(), Keys>), grid, dim3(ATT_THREADS), 0, s, p);
+  else hipLaunchKernelGGL((pgca_pairs_kernel<float, 128, pairs_qt<float>(), Keys>), grid, dim3(ATT_THREADS), 0, s, p);
 }
 
-}  // namespace
-
-extern "C" int dl_pgca_pairs_fwd(const dl_pgca_pairs_args* a, dl_stream stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const char* who = "dl_pgca_pairs_fwd";
-  DL_CHECK_ARG(a, DL_ERR_ARG, "%s: null argument block", who);
+// What dl_pgca_pairs_args and dl_pgca_pairs_ragged_args share (same field names): the checks, and the common block of the
+// launch.  st / stn: the entry point's strides and their names, left_es and left_rs at st[left_at] and st[left_at + 1].
+// Nothing behind a pointer is looked at, and with n_pairs == 0 (no launch) no pointer or stride either.
+template <typename Args>
+int pairs_common(const char* who, const Args* a, const int64_t* st, const char* const* stn, int n_st, int left_at, PairsCommon& p) {
   DL_CHECK_ARG(a->dtype == DL_F32 || a->dtype == DL_BF16, DL_ERR_ARG, "%s: bad dtype %d", who, a->dtype);
   DL_CHECK_ARG(a->head_dim == 128, DL_ERR_UNSUPPORTED, "%s: head_dim %d (one head of 128 only)", who, a->head_dim);
   DL_CHECK_ARG(a->n_pairs >= 0 && a->n_q >= 0 && a->n_kv >= 0, DL_ERR_SHAPE, "%s: negative count (n_pairs %d, n_q %d, n_kv %d)", who,
                a->n_pairs, a->n_q, a->n_kv);
-  DL_CHECK_ARG(a->Lq > 0 && a->Lk > 0, DL_ERR_SHAPE, "%s: Lq %d, Lk %d must be positive", who, a->Lq, a->Lk);
-  DL_CHECK_ARG(a->key_tail_rows >= 0 && a->key_tail_rows <= a->Lk, DL_ERR_ARG, "%s: key_tail_rows %d not in [0, Lk = %d]", who,
-               a->key_tail_rows, a->Lk);
-  DL_CHECK_ARG(a->key_tail_rows == 0 || a->key_tail_weight >= 1.f, DL_ERR_ARG, "%s: key_tail_weight %g below 1", who,
-               (double)a->key_tail_weight);
+  DL_CHECK_ARG(a->Lq > 0, DL_ERR_SHAPE, "%s: Lq %d must be positive", who, a->Lq);
   DL_CHECK_ARG(a->scale > 0.f, DL_ERR_ARG, "%s: scale must be positive", who);
   DL_CHECK_ARG(a->left_cols >= 0 && a->left_cols % 8 == 0, DL_ERR_ALIGN, "%s: left_cols %d not a non-negative multiple of 8 elements", who,
                a->left_cols);
@@ -251,10 +230,8 @@ extern "C" int dl_pgca_pairs_fwd(const dl_pgca_pairs_args* a, dl_stream stream) 
   if (a->n_pairs == 0) return DL_OK;
   DL_CHECK_ARG(a->Q && a->K && a->V && a->out && a->q_index && a->kv_index, DL_ERR_ARG, "%s: null pointer (Q, K, V, out, q_index, kv_index)", who);
   const int epc = 16 / (int)dl_dtype_size(a->dtype);
-  const int64_t st[] = {a->q_es, a->q_rs, a->k_es, a->k_rs, a->v_es, a->v_rs, a->left_es, a->left_rs, a->out_ps, a->out_rs};
-  const char* stn[] = {"q_es", "q_rs", "k_es", "k_rs", "v_es", "v_rs", "left_es", "left_rs", "out_ps", "out_rs"};
-  for (int i = 0; i < 10; ++i) {
-    if (!a->left && (i == 6 || i == 7)) continue;       // (left_es / left_rs are not read without left)
+  for (int i = 0; i < n_st; ++i) {
+    if (!a->left && (i == left_at || i == left_at + 1)) continue;       // (left_es / left_rs are not read without left)
     DL_CHECK_ARG(st[i] >= 0 && st[i] % epc == 0, DL_ERR_ALIGN, "%s: stride %s (%ld) not a non-negative multiple of %d elements", who,
                  stn[i], (long)st[i], epc);
   }
@@ -267,19 +244,59 @@ extern "C" int dl_pgca_pairs_fwd(const dl_pgca_pairs_args* a, dl_stream stream) 
   const int qt = a->dtype == DL_BF16 ? pairs_qt<bf16_t>() : pairs_qt<float>();
   const int bps = (a->Lq + 64 * qt - 1) / (64 * qt);
   DL_CHECK_ARG((int64_t)a->n_pairs * bps <= INT32_MAX, DL_ERR_SHAPE, "%s: too many workgroups (%d pairs x %d)", who, a->n_pairs, bps);
-  PairsP p = {};
   p.Q = (const char*)a->Q; p.K = (const char*)a->K; p.V = (const char*)a->V; p.left = (const char*)a->left;
   p.out = (char*)a->out; p.bias = a->bias; p.qi = a->q_index; p.ki = a->kv_index; p.flags = a->flags;
-  p.q_es = a->q_es; p.q_rs = a->q_rs; p.k_es = a->k_es; p.k_rs = a->k_rs; p.v_es = a->v_es; p.v_rs = a->v_rs;
+  p.q_es = a->q_es; p.q_rs = a->q_rs; p.k_rs = a->k_rs; p.v_rs = a->v_rs;
   p.left_es = a->left_es; p.left_rs = a->left_rs; p.out_ps = a->out_ps; p.out_rs = a->out_rs;
-  p.n_q = a->n_q; p.n_kv = a->n_kv; p.Lq = a->Lq; p.Lk = a->Lk; p.bps = bps;
+  p.n_q = a->n_q; p.n_kv = a->n_kv; p.Lq = a->Lq; p.bps = bps;
   p.left_chunks = a->left ? a->left_cols / epc : 0;
   p.out_col0 = a->out_col0;
   p.scale = a->scale;
-  p.tail_start = a->Lk - a->key_tail_rows;
-  p.tail_bias = a->key_tail_rows ? logf(a->key_tail_weight) / a->scale : 0.f;
-  if (a->dtype == DL_BF16) launch_pairs<bf16_t>(p, a->n_pairs, s);
-  else launch_pairs<float>(p, a->n_pairs, s);
+  return DL_OK;
+}
+
+}  // namespace
+
+extern "C" int dl_pgca_pairs_fwd(const dl_pgca_pairs_args* a, dl_stream stream) {
+  const char* who = "dl_pgca_pairs_fwd";
+  DL_CHECK_ARG(a, DL_ERR_ARG, "%s: null argument block", who);
+  DL_CHECK_ARG(a->Lq > 0 && a->Lk > 0, DL_ERR_SHAPE, "%s: Lq %d, Lk %d must be positive", who, a->Lq, a->Lk);
+  DL_CHECK_ARG(a->key_tail_rows >= 0 && a->key_tail_rows <= a->Lk, DL_ERR_ARG, "%s: key_tail_rows %d not in [0, Lk = %d]", who,
+               a->key_tail_rows, a->Lk);
+  DL_CHECK_ARG(a->key_tail_rows == 0 || a->key_tail_weight >= 1.f, DL_ERR_ARG, "%s: key_tail_weight %g below 1", who,
+               (double)a->key_tail_weight);
+  const int64_t st[] = {a->q_es, a->q_rs, a->k_es, a->k_rs, a->v_es, a->v_rs, a->left_es, a->left_rs, a->out_ps, a->out_rs};
+  const char* stn[] = {"q_es", "q_rs", "k_es", "k_rs", "v_es", "v_rs", "left_es", "left_rs", "out_ps", "out_rs"};
+  PairsP<DenseKeys> p = {};
+  const int rc = pairs_common(who, a, st, stn, 10, 6, p);
+  if (rc != DL_OK || a->n_pairs == 0) return rc;
+  p.keys.k_es = a->k_es; p.keys.v_es = a->v_es;
+  p.keys.Lk = a->Lk;
+  p.keys.tail_start = a->Lk - a->key_tail_rows;
+  p.keys.tail_bias = a->key_tail_rows ? logf(a->key_tail_weight) / a->scale : 0.f;
+  launch_pairs(a->dtype, p, a->n_pairs, (hipStream_t)stream);
   DL_CHECK_LAUNCH("dl_pgca_pairs_fwd");
+  return DL_OK;
+}
+
+extern "C" int dl_pgca_pairs_ragged_fwd(const dl_pgca_pairs_ragged_args* a, dl_stream stream) {
+  const char* who = "dl_pgca_pairs_ragged_fwd";
+  DL_CHECK_ARG(a, DL_ERR_ARG, "%s: null argument block", who);
+  DL_CHECK_ARG(a->kv_total_rows >= 0, DL_ERR_SHAPE, "%s: kv_total_rows %ld is negative", who, (long)a->kv_total_rows);
+  DL_CHECK_ARG(a->key_tail_rows >= 0, DL_ERR_ARG, "%s: key_tail_rows %d is negative", who, a->key_tail_rows);
+  const int64_t st[] = {a->q_es, a->q_rs, a->k_rs, a->v_rs, a->left_es, a->left_rs, a->out_ps, a->out_rs};
+  const char* stn[] = {"q_es", "q_rs", "k_rs", "v_rs", "left_es", "left_rs", "out_ps", "out_rs"};
+  PairsP<RaggedKeys> p = {};
+  const int rc = pairs_common(who, a, st, stn, 8, 4, p);
+  if (rc != DL_OK || a->n_pairs == 0) return rc;
+  DL_CHECK_ARG(a->kv_row0 && a->kv_keys && a->kv_tail_weight, DL_ERR_ARG, "%s: null pointer (kv_row0, kv_keys, kv_tail_weight)", who);
+  DL_CHECK_ARG(((uintptr_t)a->kv_row0 & 7) == 0, DL_ERR_ALIGN, "%s: kv_row0 not 8-byte aligned", who);
+  DL_CHECK_ARG((((uintptr_t)a->kv_keys | (uintptr_t)a->kv_tail_weight) & 3) == 0, DL_ERR_ALIGN,
+               "%s: kv_keys / kv_tail_weight not 4-byte aligned", who);
+  p.keys.row0 = a->kv_row0; p.keys.keys = a->kv_keys; p.keys.tailw = a->kv_tail_weight;
+  p.keys.total_rows = a->kv_total_rows;
+  p.keys.tail_rows = a->key_tail_rows;
+  launch_pairs(a->dtype, p, a->n_pairs, (hipStream_t)stream);
+  DL_CHECK_LAUNCH("dl_pgca_pairs_ragged_fwd");
   return DL_OK;
 }

@@ -1,4 +1,5 @@
-// tiles.cuh — LDS tile image + MFMA fragment loaders shared by the attention and NT-Xent kernels.
+// tiles.cuh — LDS tile image + MFMA fragment loaders shared by the attention and NT-Xent kernels, the LDS-DMA row loader
+// of the attention kernels and the three tile steps of the streamed forward.
 // Tiles are [rows][HD] with 16-byte chunks XOR-swizzled by ATile::swz(row); the same image serves
 // ds_read_b128 (K-contiguous fragments) and ds_read_b64_tr_b16 / ds_read_b32 (transposed fragments).
 #pragma once
@@ -100,6 +101,98 @@ __device__ __forceinline__ u32x4 frag_from_acc(const f32x4* t) {
   else return ctile_frag_f32(t[0]);
 }
 
+// v_exp_f32 without libm's denormal-range fix-up (arguments here are <= 0 and results below 2^-126 may flush);
+// exp2(-inf) = 0 as the online softmax needs
+__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// what the LDS-DMA loaders read for a row past the end of its tensor (const: every translation unit keeps its own copy)
+__device__ __attribute__((aligned(16))) const uint32_t zero_page[4] = {0u, 0u, 0u, 0u};
+
+// LDS-DMA of `total_rows` (a multiple of 64) rows of head_dim elements into an ATile image: source-side XOR
+// swizzle, rows >= valid_rows read the zero page.  NT threads; complete for the workgroup after vm_wait<0>() + __syncthreads().
+template <typename T, int HD, int NT>
+__device__ __forceinline__ void dma_rows(char* lds, const T* base, int64_t row_stride, int valid_rows, int total_rows) {
+  using TL = ATile<T, HD>;
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int nchunks = total_rows * TL::CPR;
+  const char* zero = reinterpret_cast<const char*>(zero_page);
+  for (int c0 = 0; c0 < nchunks; c0 += NT) {
+    const int c = c0 + tid;
+    const int row = c / TL::CPR, ch = (c % TL::CPR) ^ TL::swz(row);
+    const char* src = (c < nchunks && row < valid_rows) ? reinterpret_cast<const char*>(base + (int64_t)row * row_stride + ch * TL::EPC) : zero;
+    const uint32_t off = __builtin_amdgcn_readfirstlane((uint32_t)((c0 + wave * 64) * 16));
+    if (c0 + wave * 64 < nchunks)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                       (__attribute__((address_space(3))) void*)(lds + off), 16, 0, 0);
+  }
+}
+
+// ---- the three steps of the streamed forward on one tile of 16 * NKT keys, transposed layout: lane (il, g) holds keys
+//      kt * 16 + 4 g + r of query il for each of the wave's QT 16-query tiles.  Raw-logit stores, key masking and the tail
+//      bias go between the first and the second at the call site. ----
+// S^T = K Q^T: K fragments from the LDS tile, Q fragments from registers
+template <typename T, int HD, int QT, int NKT>
+__device__ __forceinline__ void fwd_scores(const char* Ks, const u32x4 (&qf)[QT][HD / Mma<T>::KF], f32x4 (&s)[QT][NKT], int il, int g) {
+  constexpr int NKF = HD / Mma<T>::KF;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) s[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kf = 0; kf < NKF; ++kf) {
+      const u32x4 ka = frag_kc<T, HD>(Ks, kt * 16, kf, il, g);
+#pragma unroll
+      for (int qt = 0; qt < QT; ++qt) s[qt][kt] = Mma<T>::mma(ka, qf[qt][kf], s[qt][kt]);
+    }
+  }
+}
+// online softmax (per q = il; replicated over g): s becomes exp2(s * c - m_new * c), the running maximum and sum move on
+// and o is rescaled
+template <int QT, int NKT, int NDT>
+__device__ __forceinline__ void fwd_softmax(f32x4 (&s)[QT][NKT], float (&m_run)[QT], float (&l_run)[QT], f32x4 (&o)[NDT][QT], float c) {
+#pragma unroll
+  for (int qt = 0; qt < QT; ++qt) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[qt][kt][r]);
+    mx = group4_max(mx);
+    const float m_new = fmaxf(m_run[qt], mx);
+    const float alpha = fast_exp2((m_run[qt] - m_new) * c);
+    const float mc = m_new * c;
+    float rs = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = fast_exp2(s[qt][kt][r] * c - mc);
+        s[qt][kt][r] = e;
+        rs += e;
+      }
+    l_run[qt] = l_run[qt] * alpha + rs;   // per-lane partial (own keys); reduced at the end
+    m_run[qt] = m_new;
+#pragma unroll
+    for (int d = 0; d < NDT; ++d) o[d][qt] *= alpha;
+  }
+}
+// O^T += V^T P^T: P^T straight from the accumulators, V^T by the LDS transpose read
+template <typename T, int HD, int QT, int NKT>
+__device__ __forceinline__ void fwd_accumulate(const char* Vs, const f32x4 (&s)[QT][NKT], f32x4 (&o)[HD / 16][QT], int il, int g) {
+  constexpr int KF = Mma<T>::KF, NDT = HD / 16, CT = KF / 16, NKP = NKT * 16 / KF;
+#pragma unroll
+  for (int kp = 0; kp < NKP; ++kp) {
+    u32x4 pb[QT];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) pb[qt] = frag_from_acc<T>(&s[qt][kp * CT]);
+#pragma unroll
+    for (int d = 0; d < NDT; ++d) {
+      const u32x4 va = frag_tr<T, HD>(Vs, kp * KF, d * 16, il, g);
+#pragma unroll
+      for (int qt = 0; qt < QT; ++qt) o[d][qt] = Mma<T>::mma(va, pb[qt], o[d][qt]);
+    }
+  }
+}
 
 // ---- LDS-DMA as inline assembly (invisible to the compiler's wait-count model: counted vmcnt waits stay counted) ----
 // one instruction = 64 lanes x 16 (4) bytes -> 1 KB (256 B) of LDS at lds_off + 16 (4) * lane

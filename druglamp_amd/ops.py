@@ -461,6 +461,46 @@ def attn_probs(q, k, *, n_problems, n_heads, n_segments, partner_shift, Lq, Lk, 
     return out
 
 
+def _pgca_pairs_common(who, a, q, store, store_name, store_dims, q_index, kv_index, scale, left, bias, out):
+    """What pgca_pairs and pgca_pairs_ragged share: the checks of q, of the [K | V'] store (store_name and the names of its
+    leading dimensions are what the messages call it), of the index vectors, left and bias; out, allocated or validated; the
+    fields that PgcaPairsArgs and PgcaPairsRaggedArgs have in common, filled into `a`.  Returns out."""
+    if (q.dim() != 3 or store.dim() != len(store_dims) + 1 or q.shape[2] != 128 or store.shape[-1] != 256 or q.stride(2) != 1
+            or store.stride(-1) != 1):
+        raise ValueError("%s: q must be (n_q, Lq, 128) and %s (%s, 256) with contiguous columns" % (who, store_name, ", ".join(store_dims)))
+    if store.dtype != q.dtype:
+        raise ValueError("%s: q is %s, %s is %s" % (who, q.dtype, store_name, store.dtype))
+    for t in (q_index, kv_index):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != q_index.numel():
+            raise ValueError("%s: q_index / kv_index must be contiguous int32 vectors of one length" % who)
+    n_pairs, (n_q, Lq, E) = q_index.numel(), q.shape
+    left_cols = 0
+    if left is not None:
+        if left.dim() != 3 or left.shape[:2] != q.shape[:2] or left.dtype != q.dtype or left.stride(2) != 1:
+            raise ValueError("%s: left must be (n_q, Lq, cols) of q's dtype with contiguous columns" % who)
+        left_cols = left.shape[2]
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != E or not bias.is_contiguous()):
+        raise ValueError("%s: bias must be a contiguous float32 vector of %d" % (who, E))
+    cols = left_cols + E
+    if out is None:
+        out = torch.empty((n_pairs, Lq, cols), dtype=q.dtype, device=q.device)
+    elif (out.dim() != 3 or out.dtype != q.dtype or out.device != q.device or out.shape[0] != n_pairs or out.shape[1] != Lq
+          or out.shape[2] < cols or out.stride(2) != 1 or out.stride(1) < cols or (n_pairs > 1 and out.stride(0) < (Lq - 1) * out.stride(1) + cols)):
+        raise ValueError("%s: out must be a %s tensor of (%d, %d, >= %d) on q's device with contiguous columns and "
+                         "non-overlapping rows (got %s, strides %s)" % (who, q.dtype, n_pairs, Lq, cols, tuple(out.shape), out.stride()))
+    a.Q, a.K, a.V, a.left, a.out, a.bias = q.data_ptr(), store.data_ptr(), store.data_ptr() + E * store.element_size(), _ptr(left), out.data_ptr(), _ptr(bias)
+    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
+    a.q_es, a.q_rs = q.stride(0), q.stride(1)
+    a.k_rs = a.v_rs = store.stride(-2)
+    if left is not None:
+        a.left_es, a.left_rs = left.stride(0), left.stride(1)
+    a.out_ps, a.out_rs = out.stride(0), out.stride(1)
+    a.n_pairs, a.n_q, a.Lq, a.head_dim, a.dtype = n_pairs, n_q, Lq, E, _dt(q)
+    a.left_cols, a.out_col0 = left_cols, left_cols
+    a.scale = float(scale)
+    return out
+
+
 def pgca_pairs(q, kv, q_index, kv_index, *, scale, left=None, bias=None, key_tail=None, out=None):
     """The pair-indexed PGCA attention core over cached entity codes (dl_pgca_pairs_fwd).  q (n_q, Lq, 128): the projected
     queries per protein; kv (n_kv, Lk, 256) = [K | V']: the projected keys and the values behind the out-projection per drug
@@ -470,40 +510,10 @@ def pgca_pairs(q, kv, q_index, kv_index, *, scale, left=None, bias=None, key_tai
     + 128) is allocated unless given; a caller's out may have wider rows.  key_tail = (rows, weight) as in attn_fwd.  A pair
     with an index out of range is skipped and sets FLAG_PAIR_INDEX in the device guard word (check_guard_flags)."""
     _need_gpu(q, kv, q_index, kv_index, left, bias, out)
-    if q.dim() != 3 or kv.dim() != 3 or q.shape[2] != 128 or kv.shape[2] != 256 or q.stride(2) != 1 or kv.stride(2) != 1:
-        raise ValueError("pgca_pairs: q must be (n_q, Lq, 128) and kv (n_kv, Lk, 256) with contiguous columns")
-    if kv.dtype != q.dtype:
-        raise ValueError("pgca_pairs: q is %s, kv is %s" % (q.dtype, kv.dtype))
-    for t in (q_index, kv_index):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != q_index.numel():
-            raise ValueError("pgca_pairs: q_index / kv_index must be contiguous int32 vectors of one length")
-    n_pairs, (n_q, Lq, E), (n_kv, Lk, _) = q_index.numel(), q.shape, kv.shape
-    left_cols = 0
-    if left is not None:
-        if left.dim() != 3 or left.shape[:2] != q.shape[:2] or left.dtype != q.dtype or left.stride(2) != 1:
-            raise ValueError("pgca_pairs: left must be (n_q, Lq, cols) of q's dtype with contiguous columns")
-        left_cols = left.shape[2]
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != E or not bias.is_contiguous()):
-        raise ValueError("pgca_pairs: bias must be a contiguous float32 vector of %d" % E)
-    cols = left_cols + E
-    if out is None:
-        out = torch.empty((n_pairs, Lq, cols), dtype=q.dtype, device=q.device)
-    elif (out.dim() != 3 or out.dtype != q.dtype or out.device != q.device or out.shape[0] != n_pairs or out.shape[1] != Lq
-          or out.shape[2] < cols or out.stride(2) != 1 or out.stride(1) < cols or (n_pairs > 1 and out.stride(0) < (Lq - 1) * out.stride(1) + cols)):
-        raise ValueError("pgca_pairs: out must be a %s tensor of (%d, %d, >= %d) on q's device with contiguous columns and "
-                         "non-overlapping rows (got %s, strides %s)" % (q.dtype, n_pairs, Lq, cols, tuple(out.shape), out.stride()))
     a = PgcaPairsArgs()
-    a.Q, a.K, a.V, a.left, a.out, a.bias = q.data_ptr(), kv.data_ptr(), kv.data_ptr() + E * kv.element_size(), _ptr(left), out.data_ptr(), _ptr(bias)
-    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
-    a.q_es, a.q_rs = q.stride(0), q.stride(1)
-    a.k_es, a.k_rs = kv.stride(0), kv.stride(1)
-    a.v_es, a.v_rs = kv.stride(0), kv.stride(1)
-    if left is not None:
-        a.left_es, a.left_rs = left.stride(0), left.stride(1)
-    a.out_ps, a.out_rs = out.stride(0), out.stride(1)
-    a.n_pairs, a.n_q, a.n_kv, a.Lq, a.Lk, a.head_dim, a.dtype = n_pairs, n_q, n_kv, Lq, Lk, E, _dt(q)
-    a.left_cols, a.out_col0 = left_cols, left_cols
-    a.scale = float(scale)
+    out = _pgca_pairs_common("pgca_pairs", a, q, kv, "kv", ("n_kv", "Lk"), q_index, kv_index, scale, left, bias, out)
+    a.k_es = a.v_es = kv.stride(0)
+    a.n_kv, a.Lk = kv.shape[:2]
     if key_tail is not None:
         a.key_tail_rows, a.key_tail_weight = int(key_tail[0]), float(key_tail[1])
     check(_lib.lib().dl_pgca_pairs_fwd(C.byref(a), _stream()), "dl_pgca_pairs_fwd")
@@ -518,47 +528,16 @@ def pgca_pairs_ragged(q, rows, row0, n_keys, tail_weight, q_index, kv_index, *, 
     A pair with an index out of range sets FLAG_PAIR_INDEX, one whose drug's table entry does not describe rows inside
     `rows` sets FLAG_KEY_TABLE in the device guard word (check_guard_flags); either pair is skipped."""
     _need_gpu(q, rows, row0, n_keys, tail_weight, q_index, kv_index, left, bias, out)
-    if q.dim() != 3 or rows.dim() != 2 or q.shape[2] != 128 or rows.shape[1] != 256 or q.stride(2) != 1 or rows.stride(1) != 1:
-        raise ValueError("pgca_pairs_ragged: q must be (n_q, Lq, 128) and rows (R, 256) with contiguous columns")
-    if rows.dtype != q.dtype:
-        raise ValueError("pgca_pairs_ragged: q is %s, rows is %s" % (q.dtype, rows.dtype))
-    for t in (q_index, kv_index):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != q_index.numel():
-            raise ValueError("pgca_pairs_ragged: q_index / kv_index must be contiguous int32 vectors of one length")
     for t, dt, what in ((row0, torch.int64, "row0 int64"), (n_keys, torch.int32, "n_keys int32"), (tail_weight, torch.float32, "tail_weight float32")):
         if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() != row0.numel() or t.device != q.device:
             raise ValueError("pgca_pairs_ragged: the key table is three contiguous vectors of one length on q's device "
                              "(row0 int64, n_keys int32, tail_weight float32); %s is %s %s" % (what, t.dtype, tuple(t.shape)))
     if int(key_tail_rows) < 0:
         raise ValueError("pgca_pairs_ragged: key_tail_rows %d is negative" % int(key_tail_rows))
-    n_pairs, (n_q, Lq, E), n_kv = q_index.numel(), q.shape, row0.numel()
-    left_cols = 0
-    if left is not None:
-        if left.dim() != 3 or left.shape[:2] != q.shape[:2] or left.dtype != q.dtype or left.stride(2) != 1:
-            raise ValueError("pgca_pairs_ragged: left must be (n_q, Lq, cols) of q's dtype with contiguous columns")
-        left_cols = left.shape[2]
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != E or not bias.is_contiguous()):
-        raise ValueError("pgca_pairs_ragged: bias must be a contiguous float32 vector of %d" % E)
-    cols = left_cols + E
-    if out is None:
-        out = torch.empty((n_pairs, Lq, cols), dtype=q.dtype, device=q.device)
-    elif (out.dim() != 3 or out.dtype != q.dtype or out.device != q.device or out.shape[0] != n_pairs or out.shape[1] != Lq
-          or out.shape[2] < cols or out.stride(2) != 1 or out.stride(1) < cols or (n_pairs > 1 and out.stride(0) < (Lq - 1) * out.stride(1) + cols)):
-        raise ValueError("pgca_pairs_ragged: out must be a %s tensor of (%d, %d, >= %d) on q's device with contiguous columns and "
-                         "non-overlapping rows (got %s, strides %s)" % (q.dtype, n_pairs, Lq, cols, tuple(out.shape), out.stride()))
     a = PgcaPairsRaggedArgs()
-    a.Q, a.K, a.V, a.left, a.out, a.bias = q.data_ptr(), rows.data_ptr(), rows.data_ptr() + E * rows.element_size(), _ptr(left), out.data_ptr(), _ptr(bias)
-    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
+    out = _pgca_pairs_common("pgca_pairs_ragged", a, q, rows, "rows", ("R",), q_index, kv_index, scale, left, bias, out)
     a.kv_row0, a.kv_keys, a.kv_tail_weight = row0.data_ptr(), n_keys.data_ptr(), tail_weight.data_ptr()
-    a.q_es, a.q_rs = q.stride(0), q.stride(1)
-    a.k_rs = a.v_rs = rows.stride(0)
-    if left is not None:
-        a.left_es, a.left_rs = left.stride(0), left.stride(1)
-    a.out_ps, a.out_rs = out.stride(0), out.stride(1)
-    a.kv_total_rows = rows.shape[0]
-    a.n_pairs, a.n_q, a.n_kv, a.Lq, a.head_dim, a.dtype = n_pairs, n_q, n_kv, Lq, E, _dt(q)
-    a.left_cols, a.out_col0 = left_cols, left_cols
-    a.scale = float(scale)
+    a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
     a.key_tail_rows = int(key_tail_rows)
     check(_lib.lib().dl_pgca_pairs_ragged_fwd(C.byref(a), _stream()), "dl_pgca_pairs_ragged_fwd")
     return out

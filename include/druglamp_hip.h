@@ -385,6 +385,8 @@ int dl_pgca_pairs_fwd(const dl_pgca_pairs_args* a, dl_stream s);
  * Pair-indexed PGCA attention core over a packed per-drug row store (forward only): the resident
  * drug library of the screening path.  dl_pgca_pairs_fwd takes one Lk and one key_tail_weight for the
  * whole launch; here every drug has its own key count and multiplicity, read from a device table.
+ * Both entry points launch the same kernel (csrc/pgca_pairs.hip), which differs only in where a
+ * workgroup finds its keys: on a store of equal-length drugs with w_d = 1 they give the same bits.
  *
  * K and V point into one row store of kv_total_rows rows ([K | V'] with row strides k_rs, v_rs).
  * Drug d < n_kv owns the segment of Lk_d = kv_keys[d] rows that starts at row kv_row0[d]; each of the

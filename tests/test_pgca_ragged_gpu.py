@@ -1,4 +1,4 @@
-"""dl_pgca_pairs_ragged_fwd (csrc/pgca_pairs_ragged.hip) through ops.pgca_pairs_ragged, element-wise against the fp64 reference of
+"""dl_pgca_pairs_ragged_fwd (csrc/pgca_pairs.hip, RaggedKeys) through ops.pgca_pairs_ragged, element-wise against the fp64 reference of
 tests/attn_ref.py run per pair on the explicitly gathered Q[pi] and that drug's own rows, Lk_d and (key_tail_rows, w_d).
 
 Bound: |O - ref| <= tau_O (mag_O + |bias|), the rounding model written out in tests/test_attention_paths_gpu.py and restated
@@ -227,6 +227,32 @@ def test_two_calls_are_bitwise_identical():
     s = _setup("a_six_layouts", BF)
     a, b = _run(s)[0], _run(s)[0]
     assert torch.equal(_bits(a), _bits(b))
+
+
+@pytest.mark.parametrize("dt", [BF, F32], ids=["bfloat16", "float32"])
+def test_dense_and_ragged_entry_points_agree_bitwise_on_a_uniform_store(dt):
+    """dl_pgca_pairs_fwd and dl_pgca_pairs_ragged_fwd launch one kernel that differs only in where a workgroup finds its keys, so
+    on a store whose drugs all have Lk = 72 keys (two key tiles, the second partial) the two must give the same bits: `kv` as
+    (3, 72, 256) for the dense entry point, the same memory as (216, 256) with row0 = (0, 72, 144) for the ragged one.  Lq = 40
+    is a partial query block in both dtypes.  Weight 1 and no tail rows: the dense tail bias is a host logf and the ragged one
+    a device logf, and equality is only guaranteed where both are exactly 0."""
+    from druglamp_amd import ops
+    g = torch.Generator().manual_seed(72)
+    n_q, n_kv, Lq, Lk = 2, 3, 40, 72
+    q = (torch.randn(n_q, Lq, E, generator=g) * 0.7).to(DEV, dt)
+    kv = torch.cat([torch.randn(n_kv, Lk, E, generator=g) * 0.7, torch.randn(n_kv, Lk, E, generator=g)], dim=2).to(DEV, dt)
+    left = torch.randn(n_q, Lq, 128, generator=g).to(DEV, dt)
+    bias = (torch.randn(E, generator=g) * 0.5).to(DEV)
+    pi = torch.tensor((0, 1, 1, 0, 1), dtype=torch.int32, device=DEV)
+    di = torch.tensor((2, 0, 1, 1, 2), dtype=torch.int32, device=DEV)
+    dense = ops.pgca_pairs(q, kv, pi, di, scale=E ** -0.5, left=left, bias=bias)
+    row0 = torch.arange(n_kv, dtype=torch.int64, device=DEV) * Lk
+    n_keys = torch.full((n_kv,), Lk, dtype=torch.int32, device=DEV)
+    w = torch.ones(n_kv, dtype=torch.float32, device=DEV)
+    ragged = ops.pgca_pairs_ragged(q, kv.view(n_kv * Lk, 2 * E), row0, n_keys, w, pi, di, scale=E ** -0.5, key_tail_rows=0, left=left, bias=bias)
+    torch.cuda.synchronize()
+    assert dense.shape == ragged.shape == (5, Lq, 128 + E) and torch.isfinite(dense.float()).all()
+    assert torch.equal(_bits(dense), _bits(ragged))
 
 
 def test_host_tensors_a_small_out_and_a_wrong_table_are_rejected():
