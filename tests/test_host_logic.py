@@ -187,6 +187,7 @@ def test_c_abi_argument_validation_without_gpu():
     assert L.dl_attn_fwd(C.byref(f), None) == -3
     assert L.dl_layernorm_fwd(p16, 6, p16, p16, p16, 6, None, None, 4, 6, 1e-6, 0, None) == -2
     assert L.dl_ntxent_fwd(p16, p16, 8, 48, 0.1, p16, p16, p16, 4096, None) == -6
+    assert L.dl_triplet_sigcos_fwd(p16, p16, p16, 2, 8193, 8, 0.3, p16, p16, p16, None) == -2 and b"n_d too large" in L.dl_last_error()
     assert L.dl_cast(p16, 0, p16, 7, 16, None) == -1
     assert L.dl_adamw_step(p16, p16, p16, p16, 16, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 0, 1.0, None, 0, None) == -1
 
