@@ -69,6 +69,7 @@ class GemmArgs(C.Structure):
 
 FLAG_PROT_PERIOD, FLAG_DRUG_TOKEN_PAD, FLAG_GCN_NODE_PAD, FLAG_PLAN_ROWS, FLAG_PAIR_INDEX = 1, 2, 4, 8, 16
 FLAG_KEY_TABLE = 32
+FLAG_MAP_COLS = 64
 TAG_OTHER, TAG_QKV_OUT, TAG_FFN, TAG_CONV, TAG_WGRAD, TAG_ADAPTOR = 0, 1, 2, 3, 4, 5
 TAG_NAMES = {0: "other", 1: "qkv_out", 2: "ffn", 3: "conv", 4: "wgrad", 5: "adaptor"}
 
@@ -148,6 +149,30 @@ class PgcaPairsRaggedArgs(C.Structure):
     ]
 
 
+class PgcaPairsProbsArgs(C.Structure):
+    _fields_ = [
+        ("Q", c_vp), ("K", c_vp), ("out", c_vp),
+        ("q_index", c_vp), ("kv_index", c_vp), ("flags", c_vp),
+        ("q_es", c_i64), ("q_rs", c_i64), ("k_es", c_i64), ("k_rs", c_i64), ("out_ps", c_i64), ("out_rs", c_i64),
+        ("n_pairs", c_i32), ("n_q", c_i32), ("n_kv", c_i32), ("Lq", c_i32), ("Lk", c_i32), ("head_dim", c_i32), ("dtype", c_i32),
+        ("out_cols", c_i32), ("expand_tail", c_i32),
+        ("scale", c_f32),
+        ("key_tail_rows", c_i32), ("key_tail_weight", c_f32),
+    ]
+
+
+class PgcaPairsRaggedProbsArgs(C.Structure):
+    _fields_ = [
+        ("Q", c_vp), ("K", c_vp), ("out", c_vp),
+        ("q_index", c_vp), ("kv_index", c_vp), ("kv_row0", c_vp), ("kv_keys", c_vp), ("kv_tail_weight", c_vp), ("flags", c_vp),
+        ("q_es", c_i64), ("q_rs", c_i64), ("k_rs", c_i64), ("out_ps", c_i64), ("out_rs", c_i64), ("kv_total_rows", c_i64),
+        ("n_pairs", c_i32), ("n_q", c_i32), ("n_kv", c_i32), ("Lq", c_i32), ("head_dim", c_i32), ("dtype", c_i32),
+        ("out_cols", c_i32), ("expand_tail", c_i32),
+        ("scale", c_f32),
+        ("key_tail_rows", c_i32),
+    ]
+
+
 class NtxentSide(C.Structure):
     _fields_ = [("q", c_vp), ("k", c_vp), ("n", c_i64), ("gid_offset", c_i64), ("lse", c_vp)]
 
@@ -188,6 +213,8 @@ SIGNATURES = {
     "dl_attn_probs": (c_i32, [C.POINTER(AttnProbsArgs), c_vp]),
     "dl_pgca_pairs_fwd": (c_i32, [C.POINTER(PgcaPairsArgs), c_vp]),
     "dl_pgca_pairs_ragged_fwd": (c_i32, [C.POINTER(PgcaPairsRaggedArgs), c_vp]),
+    "dl_pgca_pairs_probs": (c_i32, [C.POINTER(PgcaPairsProbsArgs), c_vp]),
+    "dl_pgca_pairs_ragged_probs": (c_i32, [C.POINTER(PgcaPairsRaggedProbsArgs), c_vp]),
     "dl_token_gate_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "dl_token_gate_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "dl_gate_dpre": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),

@@ -4,7 +4,8 @@
 //
 //   Pair n reads its queries from entity q_index[n] of Q and its keys / values from the segment of K / V that entity
 //   kv_index[n] owns: the operands are the cached per-entity codes (druglamp_amd/screening.py), nothing is gathered per pair.
-//   Where that segment lies is the one thing the two entry points differ in, and the kernel takes it from its `Keys` type:
+//   Where that segment lies is the one thing the two entry points differ in, and the kernel takes it from its `Keys` type
+//   (pair_keys.cuh, shared with the probability maps of pgca_pairs_probs.hip):
 //     DenseKeys  : entity d of K / V, k_es / v_es elements apart; Lk, the tail rows and their weight are launch-wide.
 //     RaggedKeys : rows kv_row0[d] .. kv_row0[d] + kv_keys[d] - 1 of one packed [K | V'] row store, whose last key_tail_rows
 //                  rows stand for kv_tail_weight[d] identical keys each (DrugLibrary); the table entry is read at the top of
@@ -23,10 +24,12 @@
 //                       A pair whose index is out of range (DL_FLAG_PAIR_INDEX), or whose drug's table entry does not
 //                       describe rows inside the store (DL_FLAG_KEY_TABLE), returns before it reads anything through the
 //                       entry or writes anything; both tests are uniform for the workgroup.
+#include "pair_keys.cuh"
 #include "tiles.cuh"
 
 namespace {
 using namespace dltile;
+using namespace dlpairs;       // KeySeg, DenseKeys, RaggedKeys: shared with pgca_pairs_probs.hip
 
 // the part of the launch that does not depend on where a pair's keys lie
 struct PairsCommon {
@@ -43,45 +46,6 @@ struct PairsCommon {
 };
 template <typename Keys> struct PairsP : PairsCommon {
   Keys keys;
-};
-
-// the keys / values of one pair, as Keys::locate() finds them
-struct KeySeg {
-  int64_t k_off, v_off;            // elements from K / V to the segment's first row
-  int Lk;
-  int tail_start;                  // Lk - key_tail_rows (== Lk: no key multiplicities)
-  float tail_bias;                 // log(w) / scale, added to the UNSCALED score of a tail key (as attention.hip)
-};
-
-struct DenseKeys {
-  int64_t k_es, v_es;
-  int Lk, tail_start;
-  float tail_bias;
-  __device__ __forceinline__ uint32_t locate(int di, int64_t, int64_t, float, KeySeg& s) const {
-    s.k_off = (int64_t)di * k_es;
-    s.v_off = (int64_t)di * v_es;
-    s.Lk = Lk; s.tail_start = tail_start; s.tail_bias = tail_bias;
-    return 0;
-  }
-};
-
-struct RaggedKeys {
-  const int64_t* row0;             // per drug: first row of its segment of the row store
-  const int32_t* keys;             //           rows of the segment (Lk_d)
-  const float* tailw;              //           multiplicity of each of the segment's last tail_rows rows
-  int64_t total_rows;
-  int tail_rows;                   // launch-wide key_tail_rows (0: no key multiplicities)
-  // an entry that does not describe rows inside the store is not used
-  __device__ __forceinline__ uint32_t locate(int di, int64_t k_rs, int64_t v_rs, float scale, KeySeg& s) const {
-    const int64_t r0 = row0[di];
-    const int Lk = keys[di];
-    const float tw = tailw[di];
-    if (r0 < 0 || Lk < max(1, tail_rows) || r0 > total_rows - (int64_t)Lk || !(tw >= 1.f && tw < INFINITY)) return DL_FLAG_KEY_TABLE;
-    s.k_off = r0 * k_rs;
-    s.v_off = r0 * v_rs;
-    s.Lk = Lk; s.tail_start = Lk - tail_rows; s.tail_bias = logf(tw) / scale;
-    return 0;
-  }
 };
 
 constexpr int KVB = 64;            // keys per streamed tile

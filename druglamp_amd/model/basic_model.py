@@ -526,23 +526,8 @@ class DrugLAMPBase(nn.Module):
     def _score_pairs(self, who, pcode, dcode, dwhat, pi, di, attend) -> torch.Tensor:
         """The pair stage behind score_codes / score_library: the checks, attend() per branch for the [sites | guided] concat,
         and the MHLA -> LayerNorm -> PMMA -> token mean -> classifier tail."""
-        self._need_eval(who)
-        for code, what in ((pcode, "protein code"), (dcode, "drug " + dwhat)):
-            if code.dtype != self.compute_dtype:
-                raise RuntimeError("%s: the %s was built in %s, the model computes in %s" % (who, what, code.dtype, self.compute_dtype))
-            if code.epoch != screening.param_epoch():
-                raise RuntimeError("%s: the %s was built before the parameters last changed (parameter epoch %d, now %d); "
-                                   "encode again" % (who, what, code.epoch, screening.param_epoch()))
-        if set(pcode.branches) != set(dcode.branches) or ("x" in pcode.branches) != self.llm_branch:
-            raise RuntimeError("%s: the codes' branches do not match the model's" % who)
-        pi_t = torch.as_tensor(pi, dtype=torch.int64, device="cpu").reshape(-1)
-        di_t = torch.as_tensor(di, dtype=torch.int64, device="cpu").reshape(-1)
-        if pi_t.numel() != di_t.numel():
-            raise ValueError("%s: %d protein indices, %d drug indices" % (who, pi_t.numel(), di_t.numel()))
+        pi_t, di_t = self._check_pairs(who, pcode, dcode, dwhat, pi, di)
         N = pi_t.numel()
-        for t, n, what in ((pi_t, pcode.n, "protein"), (di_t, dcode.n, "drug")):
-            if N and (int(t.min()) < 0 or int(t.max()) >= n):
-                raise IndexError("%s: %s index out of range [0, %d)" % (who, what, n))
         dev = pcode.branches["v"][1].device
         n_out = self.mlp_classifier.fc4.out_features
         if N == 0:
@@ -560,6 +545,61 @@ class DrugLAMPBase(nn.Module):
         with self._glue():
             score = self.mlp_classifier(Fn.TokenMeanFn.apply(f))
         return score.float()
+
+    def _check_pairs(self, who, pcode, dcode, dwhat, pi, di):
+        """The checks of every call that pairs cached codes (eval mode, compute dtype, parameter epoch, branches, index ranges);
+        returns the index sequences as flat int64 host tensors."""
+        self._need_eval(who)
+        for code, what in ((pcode, "protein code"), (dcode, "drug " + dwhat)):
+            if code.dtype != self.compute_dtype:
+                raise RuntimeError("%s: the %s was built in %s, the model computes in %s" % (who, what, code.dtype, self.compute_dtype))
+            if code.epoch != screening.param_epoch():
+                raise RuntimeError("%s: the %s was built before the parameters last changed (parameter epoch %d, now %d); "
+                                   "encode again" % (who, what, code.epoch, screening.param_epoch()))
+        if set(pcode.branches) != set(dcode.branches) or ("x" in pcode.branches) != self.llm_branch:
+            raise RuntimeError("%s: the codes' branches do not match the model's" % who)
+        pi_t = torch.as_tensor(pi, dtype=torch.int64, device="cpu").reshape(-1)
+        di_t = torch.as_tensor(di, dtype=torch.int64, device="cpu").reshape(-1)
+        if pi_t.numel() != di_t.numel():
+            raise ValueError("%s: %d protein indices, %d drug indices" % (who, pi_t.numel(), di_t.numel()))
+        N = pi_t.numel()
+        for t, n, what in ((pi_t, pcode.n, "protein"), (di_t, dcode.n, "drug")):
+            if N and (int(t.min()) < 0 or int(t.max()) >= n):
+                raise IndexError("%s: %s index out of range [0, %d)" % (who, what, n))
+        return pi_t, di_t
+
+    @torch.no_grad()
+    def cross_attn_prob_codes(self, pcode, dcode, pi, di, branch="v") -> torch.Tensor:
+        """The PGCA softmax weights of `branch` ("v", or "x" where the model has an LLM branch) for the pairs (pi[n], di[n]) of
+        cached codes: (N, n_site, cols) fp32 on the device, cols = the codes' full key count (512 on the model's path) — what
+        get_cross_attn_prob(branch) gives for those pairs after an eval forward with keep_attention_probs, from ONE
+        ops.pgca_pairs_probs launch and without that forward.  The checks are score_codes'."""
+        def maps(gca, q, pi_d, di_d, di_t):
+            d = dcode.branches[branch]
+            return ops.pgca_pairs_probs(q, d.kv, pi_d, di_d, scale=float(gca.head_dim) ** -0.5, key_tail=d.key_tail, expand_tail=True)
+        return self._pair_maps("cross_attn_prob_codes", pcode, dcode, "code", pi, di, branch, maps)
+
+    @torch.no_grad()
+    def cross_attn_prob_library(self, pcode, lib, pi, di, branch="v", cols=None) -> torch.Tensor:
+        """cross_attn_prob_codes against a resident screening.DrugLibrary (ONE ops.pgca_pairs_ragged_probs launch: every drug's map
+        comes from its own trimmed keys, expanded to its full key set in ExpandTailFn's order).  cols: the columns of a row,
+        None = the largest full key count among the drugs named (512 on the model's path); shorter maps are zero filled."""
+        def maps(gca, q, pi_d, di_d, di_t):
+            b = lib.branches[branch]
+            n = int(lib.full_keys(branch)[di_t].max()) if cols is None else int(cols)
+            return ops.pgca_pairs_ragged_probs(q, b.rows, b.row0, b.n_keys, b.tail_weight, pi_d, di_d, scale=float(gca.head_dim) ** -0.5,
+                                               key_tail_rows=screening.LIB_TAIL_ROWS, cols=n, expand_tail=True)
+        return self._pair_maps("cross_attn_prob_library", pcode, lib, "library", pi, di, branch, maps)
+
+    def _pair_maps(self, who, pcode, dcode, dwhat, pi, di, branch, maps) -> torch.Tensor:
+        if branch not in ("v", "x") or (branch == "x" and not self.llm_branch):
+            raise ValueError("%s: unknown branch %r (this model has %s)" % (who, branch, "'v' and 'x'" if self.llm_branch else "'v'"))
+        pi_t, di_t = self._check_pairs(who, pcode, dcode, dwhat, pi, di)
+        q = pcode.branches[branch][1]
+        if pi_t.numel() == 0:
+            return torch.zeros((0, q.shape[1], 0), dtype=torch.float32, device=q.device)
+        gca = self.v_gca if branch == "v" else self.x_gca
+        return maps(gca, q, pi_t.to(torch.int32).to(q.device), di_t.to(torch.int32).to(q.device), di_t)
 
     def get_cross_attn_mat(self, modality="v"):
         if modality == "v":

@@ -14,7 +14,8 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, PgcaPairsArgs, PgcaPairsRaggedArgs, check
+from ._lib import (DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, PgcaPairsArgs, PgcaPairsProbsArgs, PgcaPairsRaggedArgs,
+                   PgcaPairsRaggedProbsArgs, check)
 
 _DT = {torch.float32: DL_F32, torch.bfloat16: DL_BF16}
 
@@ -461,10 +462,8 @@ def attn_probs(q, k, *, n_problems, n_heads, n_segments, partner_shift, Lq, Lk, 
     return out
 
 
-def _pgca_pairs_common(who, a, q, store, store_name, store_dims, q_index, kv_index, scale, left, bias, out):
-    """What pgca_pairs and pgca_pairs_ragged share: the checks of q, of the [K | V'] store (store_name and the names of its
-    leading dimensions are what the messages call it), of the index vectors, left and bias; out, allocated or validated; the
-    fields that PgcaPairsArgs and PgcaPairsRaggedArgs have in common, filled into `a`.  Returns out."""
+def _check_pair_operands(who, q, store, store_name, store_dims, q_index, kv_index):
+    """The operand checks of every pair-indexed launch: q, the [K | V'] store and the index vectors."""
     if (q.dim() != 3 or store.dim() != len(store_dims) + 1 or q.shape[2] != 128 or store.shape[-1] != 256 or q.stride(2) != 1
             or store.stride(-1) != 1):
         raise ValueError("%s: q must be (n_q, Lq, 128) and %s (%s, 256) with contiguous columns" % (who, store_name, ", ".join(store_dims)))
@@ -473,6 +472,13 @@ def _pgca_pairs_common(who, a, q, store, store_name, store_dims, q_index, kv_ind
     for t in (q_index, kv_index):
         if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != q_index.numel():
             raise ValueError("%s: q_index / kv_index must be contiguous int32 vectors of one length" % who)
+
+
+def _pgca_pairs_common(who, a, q, store, store_name, store_dims, q_index, kv_index, scale, left, bias, out):
+    """What pgca_pairs and pgca_pairs_ragged share: the checks of q, of the [K | V'] store (store_name and the names of its
+    leading dimensions are what the messages call it), of the index vectors, left and bias; out, allocated or validated; the
+    fields that PgcaPairsArgs and PgcaPairsRaggedArgs have in common, filled into `a`.  Returns out."""
+    _check_pair_operands(who, q, store, store_name, store_dims, q_index, kv_index)
     n_pairs, (n_q, Lq, E) = q_index.numel(), q.shape
     left_cols = 0
     if left is not None:
@@ -528,10 +534,7 @@ def pgca_pairs_ragged(q, rows, row0, n_keys, tail_weight, q_index, kv_index, *, 
     A pair with an index out of range sets FLAG_PAIR_INDEX, one whose drug's table entry does not describe rows inside
     `rows` sets FLAG_KEY_TABLE in the device guard word (check_guard_flags); either pair is skipped."""
     _need_gpu(q, rows, row0, n_keys, tail_weight, q_index, kv_index, left, bias, out)
-    for t, dt, what in ((row0, torch.int64, "row0 int64"), (n_keys, torch.int32, "n_keys int32"), (tail_weight, torch.float32, "tail_weight float32")):
-        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() != row0.numel() or t.device != q.device:
-            raise ValueError("pgca_pairs_ragged: the key table is three contiguous vectors of one length on q's device "
-                             "(row0 int64, n_keys int32, tail_weight float32); %s is %s %s" % (what, t.dtype, tuple(t.shape)))
+    _check_key_table("pgca_pairs_ragged", q, row0, n_keys, tail_weight)
     if int(key_tail_rows) < 0:
         raise ValueError("pgca_pairs_ragged: key_tail_rows %d is negative" % int(key_tail_rows))
     a = PgcaPairsRaggedArgs()
@@ -540,6 +543,80 @@ def pgca_pairs_ragged(q, rows, row0, n_keys, tail_weight, q_index, kv_index, *, 
     a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
     a.key_tail_rows = int(key_tail_rows)
     check(_lib.lib().dl_pgca_pairs_ragged_fwd(C.byref(a), _stream()), "dl_pgca_pairs_ragged_fwd")
+    return out
+
+
+def _check_key_table(who, q, row0, n_keys, tail_weight):
+    for t, dt, what in ((row0, torch.int64, "row0 int64"), (n_keys, torch.int32, "n_keys int32"), (tail_weight, torch.float32, "tail_weight float32")):
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() != row0.numel() or t.device != q.device:
+            raise ValueError("%s: the key table is three contiguous vectors of one length on q's device "
+                             "(row0 int64, n_keys int32, tail_weight float32); %s is %s %s" % (who, what, t.dtype, tuple(t.shape)))
+
+
+def _pgca_maps_common(who, a, q, store, store_name, store_dims, q_index, kv_index, scale, cols, expand_tail, out):
+    """What pgca_pairs_probs and pgca_pairs_ragged_probs share: the checks of q, of the [K | V'] store and of the index vectors;
+    out (n_pairs, Lq, cols) fp32, allocated or validated; the fields the two argument blocks have in common.  Returns out."""
+    _check_pair_operands(who, q, store, store_name, store_dims, q_index, kv_index)
+    cols = int(cols)
+    if cols < 1:
+        raise ValueError("%s: cols %d must be positive" % (who, cols))
+    n_pairs, (n_q, Lq, E) = q_index.numel(), q.shape
+    if out is None:
+        out = torch.empty((n_pairs, Lq, cols), dtype=torch.float32, device=q.device)
+    elif (out.dim() != 3 or out.dtype != torch.float32 or out.device != q.device or out.shape[0] != n_pairs or out.shape[1] != Lq
+          or out.shape[2] < cols or out.stride(2) != 1 or out.stride(1) < cols or (n_pairs > 1 and out.stride(0) < (Lq - 1) * out.stride(1) + cols)):
+        raise ValueError("%s: out must be a float32 tensor of (%d, %d, >= %d) on q's device with contiguous columns and "
+                         "non-overlapping rows (got %s %s, strides %s)" % (who, n_pairs, Lq, cols, out.dtype, tuple(out.shape), out.stride()))
+    a.Q, a.K, a.out = q.data_ptr(), store.data_ptr(), out.data_ptr()
+    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
+    a.q_es, a.q_rs = q.stride(0), q.stride(1)
+    a.k_rs = store.stride(-2)
+    a.out_ps, a.out_rs = out.stride(0), out.stride(1)
+    a.n_pairs, a.n_q, a.Lq, a.head_dim, a.dtype = n_pairs, n_q, Lq, E, _dt(q)
+    a.out_cols, a.expand_tail = cols, int(bool(expand_tail))
+    a.scale = float(scale)
+    return out
+
+
+def pgca_pairs_probs(q, kv, q_index, kv_index, *, scale, key_tail=None, expand_tail=False, cols=None, out=None):
+    """The PGCA probability maps of (protein, drug) pairs over cached entity codes (dl_pgca_pairs_probs): pair n gets
+    softmax(scale q[qi] k[ki]^T) as fp32, k = the first 128 columns of kv (n_kv, Lk, 256) = [K | V'] as pgca_pairs takes it (the
+    values are not read).  key_tail = (rows, weight) as in attn_fwd: without expand_tail a row has Lk columns and a tail column
+    carries the mass of the keys it stands for; with expand_tail it has the full key count Lk - rows + rows * weight in
+    functional.ExpandTailFn's order (weight must be whole).  Returns (n_pairs, Lq, cols) float32; cols defaults to that column
+    count, columns beyond it are +0.0.  out: write into this tensor instead (a caller's out may have wider rows).  A pair with
+    an index out of range is skipped and sets FLAG_PAIR_INDEX in the device guard word (check_guard_flags)."""
+    _need_gpu(q, kv, q_index, kv_index, out)
+    a = PgcaPairsProbsArgs()
+    t, w = (int(key_tail[0]), float(key_tail[1])) if key_tail is not None else (0, 1.0)
+    if cols is None and kv.dim() == 3:
+        cols = kv.shape[1] - t + t * int(w) if (expand_tail and t) else kv.shape[1]
+    out = _pgca_maps_common("pgca_pairs_probs", a, q, kv, "kv", ("n_kv", "Lk"), q_index, kv_index, scale, cols or 0, expand_tail, out)
+    a.k_es = kv.stride(0)
+    a.n_kv, a.Lk = kv.shape[:2]
+    if key_tail is not None:
+        a.key_tail_rows, a.key_tail_weight = t, w
+    check(_lib.lib().dl_pgca_pairs_probs(C.byref(a), _stream()), "dl_pgca_pairs_probs")
+    return out
+
+
+def pgca_pairs_ragged_probs(q, rows, row0, n_keys, tail_weight, q_index, kv_index, *, scale, key_tail_rows, cols, expand_tail=False, out=None):
+    """pgca_pairs_probs over a packed per-drug row store (dl_pgca_pairs_ragged_probs; screening.DrugLibrary): the key table is
+    pgca_pairs_ragged's.  Drug d's map has n_keys[d] columns, or with expand_tail n_keys[d] - key_tail_rows + key_tail_rows *
+    tail_weight[d]; every row is written over `cols` columns (+0.0 behind the drug's own).  Returns (n_pairs, Lq, cols) float32.
+    A pair is skipped and flagged in the device guard word (check_guard_flags) when its index is out of range (FLAG_PAIR_INDEX),
+    its drug's table entry does not describe rows inside `rows` (FLAG_KEY_TABLE), or its map has more than `cols` columns or
+    expand_tail meets a weight that is not whole (FLAG_MAP_COLS)."""
+    _need_gpu(q, rows, row0, n_keys, tail_weight, q_index, kv_index, out)
+    _check_key_table("pgca_pairs_ragged_probs", q, row0, n_keys, tail_weight)
+    if int(key_tail_rows) < 0:
+        raise ValueError("pgca_pairs_ragged_probs: key_tail_rows %d is negative" % int(key_tail_rows))
+    a = PgcaPairsRaggedProbsArgs()
+    out = _pgca_maps_common("pgca_pairs_ragged_probs", a, q, rows, "rows", ("R",), q_index, kv_index, scale, cols, expand_tail, out)
+    a.kv_row0, a.kv_keys, a.kv_tail_weight = row0.data_ptr(), n_keys.data_ptr(), tail_weight.data_ptr()
+    a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
+    a.key_tail_rows = int(key_tail_rows)
+    check(_lib.lib().dl_pgca_pairs_ragged_probs(C.byref(a), _stream()), "dl_pgca_pairs_ragged_probs")
     return out
 
 
@@ -987,7 +1064,9 @@ FLAG_TEXT = {_lib.FLAG_PROT_PERIOD: "a protein's residue codes / fill bits are n
                                    "was skipped (dl_pgca_pairs_fwd)",
              _lib.FLAG_KEY_TABLE: "a drug's entry of a library screening launch's key table does not describe rows inside the row store "
                                   "(negative first row, fewer keys than the tail, rows past the end, or a weight that is not a finite "
-                                  "value >= 1); the pair was skipped (dl_pgca_pairs_ragged_fwd)"}
+                                  "value >= 1); the pair was skipped (dl_pgca_pairs_ragged_fwd)",
+             _lib.FLAG_MAP_COLS: "a drug's attention map of a pair-map launch does not fit the columns it was given, or its keys' "
+                                 "multiplicity cannot be expanded (not a whole number <= 2^24); the pair was skipped (dl_pgca_pairs_probs)"}
 
 
 def guard_flags(device) -> torch.Tensor:

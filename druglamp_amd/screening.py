@@ -29,6 +29,10 @@ Codes record the compute dtype and the parameter epoch (functional.bump_param_ep
                                tail_weight[d] identical keys.  A drug is trimmed to its own rows: roundup8(rows in front
                                of its trailing run of padding rows) + 8 keys instead of the batch's block + 8 or 512.
 model.score_library runs the pair stage from it with one ops.pgca_pairs_ragged launch per branch.
+
+Attention maps of pairs come from the same codes: the PGCA weights softmax(scale q K_d^T + log w) need only a ProteinCode's q and
+the first 128 columns of a drug's rows, so model.cross_attn_prob_codes / cross_attn_prob_library (one ops.pgca_pairs_probs /
+pgca_pairs_ragged_probs launch) give what get_cross_attn_prob gives after an eval forward on those pairs, without one.
 """
 from __future__ import annotations
 
@@ -228,6 +232,13 @@ class DrugLibrary:
 
     def __init__(self, branches: Dict[str, LibraryBranch], dtype: torch.dtype, epoch: int, fingerprint_: Optional[str] = None):
         self.branches, self.dtype, self.epoch, self.fingerprint = dict(branches), dtype, int(epoch), fingerprint_
+        self._count_full_keys()
+
+    def _count_full_keys(self) -> None:
+        """Per branch the full key count of every drug, (D,) int64 on the host: taken once here (from_codes, load) and after
+        append, so that a map launch sizes its columns without a device sync."""
+        T = LIB_TAIL_ROWS
+        self._full_keys = {k: (b.n_keys.to(torch.int64) - T + T * b.tail_weight.to(torch.int64)).cpu() for k, b in self.branches.items()}
 
     # ---- building -------------------------------------------------------------------------------------------------------
     @classmethod
@@ -263,6 +274,7 @@ class DrugLibrary:
             row0 = lb.rows.shape[0] + torch.cumsum(n_keys, 0) - n_keys
             self.branches[k] = LibraryBranch(torch.cat([lb.rows, rows]), torch.cat([lb.row0, row0]), torch.cat([lb.n_keys, n_keys.to(torch.int32)]),
                                              torch.cat([lb.tail_weight, weight]), lb.bias)
+        self._count_full_keys()
         return self
 
     # ---- what it holds --------------------------------------------------------------------------------------------------
@@ -278,6 +290,11 @@ class DrugLibrary:
     def keys(self, branch: str = "v") -> torch.Tensor:
         """The stored key count of every drug, (D,) int32."""
         return self.branches[branch].n_keys
+
+    def full_keys(self, branch: str = "v") -> torch.Tensor:
+        """The full key count n_keys - 8 + 8 * tail_weight of every drug, (D,) int64 on the host: the columns of its expanded
+        attention map (512 on the model's path)."""
+        return self._full_keys[branch]
 
     def expand(self, branch: str, i: int) -> torch.Tensor:
         """Drug i's code over its full key set (lead + 8 * weight rows, 512 on the model's path) in ExpandTailFn's order: tail row

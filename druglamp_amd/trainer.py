@@ -1046,6 +1046,49 @@ class Trainer:
                     torch.zeros((0, int(top_k)), dtype=torch.int64, device=self.device))
         return torch.cat(vals).contiguous(), torch.cat(idxs).contiguous()
 
+    @torch.no_grad()
+    def hit_maps(self, protein_batches, lib, indices, branch: str = "v", pair_batch: int = 64) -> torch.Tensor:
+        """The PGCA attention maps of screening hits: for protein p and its j-th hit, drug indices[p, j] of the library (the
+        (P, k) int64 indices of screen_library(top_k=k)), the softmax weights of `branch` that get_cross_attn_prob gives after an
+        eval forward on that pair — which drug atoms / tokens each protein site attends to.  Returns (P, k, n_site, cols) fp32
+        on the CPU, cols = the largest full key count among the hits (512 on the model's path).  The protein batches are
+        streamed as in screen_library (the same ones, in the same order); the maps come straight from the cached codes
+        (model.cross_attn_prob_library), pair_batch pairs at a time, each chunk copied to the host: device memory holds
+        O(pair_batch) maps whatever P and k."""
+        if pair_batch < 1:
+            raise ValueError("hit_maps: pair_batch must be positive")
+        if branch not in lib.branches:
+            raise ValueError("hit_maps: unknown branch %r (the library has %s)" % (branch, sorted(lib.branches)))
+        idx = torch.as_tensor(indices, dtype=torch.int64).cpu()
+        if idx.dim() != 2:
+            raise ValueError("hit_maps: indices must be (P, k), got %s" % (tuple(idx.shape),))
+        P, k = idx.shape
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= lib.n):
+            raise IndexError("hit_maps: drug index out of range [0, %d)" % lib.n)
+        cols = int(lib.full_keys(branch)[idx.reshape(-1)].max()) if idx.numel() else 0
+        self.model.eval()
+        out, p0 = None, 0
+        for feat_p, llm_p in protein_batches:
+            pcode = self.model.encode_proteins(feat_p, llm_p)
+            Pn = pcode.n
+            if p0 + Pn > P:
+                raise ValueError("hit_maps: indices has %d rows, the protein batches yield more proteins" % P)
+            if out is None:
+                out = torch.empty((P * k, pcode.branches["v"][1].shape[1], cols), dtype=torch.float32)
+            pi = torch.arange(Pn).repeat_interleave(k)
+            di = idx[p0:p0 + Pn].reshape(-1)
+            for s in range(0, Pn * k, pair_batch):
+                m = self.model.cross_attn_prob_library(pcode, lib, pi[s:s + pair_batch], di[s:s + pair_batch], branch=branch, cols=cols)
+                out[p0 * k + s:p0 * k + s + m.shape[0]].copy_(m)
+            p0 += Pn
+            del pcode
+        if p0 != P:
+            raise ValueError("hit_maps: indices has %d rows, the protein batches yielded %d proteins" % (P, p0))
+        self.check_device_flags()
+        if out is None:
+            return torch.zeros((0, k, 0, 0), dtype=torch.float32)
+        return out.view(P, k, out.shape[1], cols)
+
     def evaluate(self, batches) -> Dict[str, float]:
         """Metrics over the union of all ranks' samples (the reference's torchmetrics objects gather their states at
         epoch end, trainer.py:262-292; its logged loss is `sync_dist=True`): ranks may hold different numbers of samples."""

@@ -429,6 +429,72 @@ typedef struct {
 } dl_pgca_pairs_ragged_args;
 int dl_pgca_pairs_ragged_fwd(const dl_pgca_pairs_ragged_args* a, dl_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Pair-indexed PGCA probability maps: the softmax weights of the two attention cores above, as fp32,
+ * straight from the cached per-entity operands (csrc/pgca_pairs_probs.hip).  What the reference hands
+ * back for interpretation (get_cross_attn_prob: which drug atoms / tokens each protein site attends to)
+ * for the (protein, drug) pairs of a screen.  No value row is read; there is no V, left or bias.
+ *
+ * dl_pgca_pairs_probs takes dense codes (one Lk, key_tail_rows = t and key_tail_weight = w for the whole
+ * launch, as dl_pgca_pairs_fwd); dl_pgca_pairs_ragged_probs takes the packed row store and its device
+ * table (kv_row0, kv_keys, kv_tail_weight, kv_total_rows, launch-wide key_tail_rows = t, as
+ * dl_pgca_pairs_ragged_fwd: drug d has Lk_d keys whose last t stand for w_d identical keys each).
+ * Both launch one kernel that differs only in where a workgroup finds its keys: on a store of
+ * equal-length drugs with w_d = 1 and t = 0 they give the same bits.
+ *
+ * For pair n < n_pairs with p = q_index[n], d = kv_index[n] (int32, device memory), lead_d = Lk_d - t:
+ *   P[r][k] = exp(scale Q[p]_r . K_d,k + log w_k - LSE_r)      (w_k = w_d on the last t keys, 1 elsewhere;
+ *                                                               LSE_r over all keys with their weights)
+ *   expand_tail == 0: out (n, r, k) = P[r][k], k < Lk_d — the softmax over the drug's DISTINCT keys; a tail
+ *                     column carries the mass of the w_d keys it stands for (any w_d >= 1)
+ *   expand_tail == 1: lead_d + t * w_d columns, the map over the FULL key set in the order the host's expansion
+ *                     of the tail uses (ExpandTailFn, DrugLibrary.expand): column lead_d + i * t + j (i < w_d,
+ *                     j < t) holds the probability of ONE copy of tail key j, exp(scale q.k_{lead_d+j} - LSE_r)
+ *   columns from the drug's count up to out_cols - 1 are written as +0.0f: every row r < Lq of a valid pair is
+ *   defined over all out_cols columns.
+ * Addressing (element strides; Q / K dtype `dtype` with contiguous columns, out fp32):
+ *   q    (e, r, :) = Q + e*q_es + r*q_rs          e < n_q
+ *   K_d  (j, :)    = K + d*k_es + j*k_rs          j < Lk            (dense)
+ *   K_d  (j, :)    = K + (kv_row0[d] + j)*k_rs    j < kv_keys[d]    (ragged)
+ *   out  (n, r, c) = out + n*out_ps + r*out_rs + c     r < Lq, c < out_cols
+ * Nothing is written at or beyond column out_cols, nothing outside the addressed rows; no row outside a pair's
+ * segment is read for it.  No atomics on out: two calls agree bitwise.
+ * A pair is skipped — nothing is read through its table entry, nothing is written for it — when
+ *   its index is outside [0, n_q) or [0, n_kv)                           -> DL_FLAG_PAIR_INDEX is OR-ed into *flags
+ *   its table entry is malformed (the conditions of dl_pgca_pairs_ragged_fwd) -> DL_FLAG_KEY_TABLE
+ *   the drug's column count exceeds out_cols, or expand_tail is set (t > 0) and
+ *   w_d is not a whole number <= 2^24                                       -> DL_FLAG_MAP_COLS
+ * (flags may be NULL).  For the dense entry point the column count and the weight are known on the host and
+ * checked there (DL_ERR_SHAPE / DL_ERR_ARG).
+ * One head, head_dim == 128 (else DL_ERR_UNSUPPORTED); Lq arbitrary; Q / K 16-byte aligned with strides multiples of
+ * 16 bytes; out 4-byte aligned, out_ps >= 0, out_rs >= out_cols > 0; 16-byte stores when out is 16-byte aligned and
+ * out_ps, out_rs are multiples of 4, 4-byte stores otherwise; kv_row0 8-byte, the other index vectors 4-byte aligned;
+ * expand_tail 0 or 1; key_tail_rows >= 0 (dense: <= Lk, key_tail_weight >= 1), kv_total_rows >= 0.
+ * n_pairs == 0: DL_OK, nothing is launched, no pointer is looked at.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* Q; const void* K; float* out;
+  const int32_t* q_index; const int32_t* kv_index; uint32_t* flags;
+  int64_t q_es, q_rs, k_es, k_rs, out_ps, out_rs;
+  int32_t n_pairs, n_q, n_kv, Lq, Lk, head_dim, dtype;
+  int32_t out_cols, expand_tail;
+  float scale;
+  int32_t key_tail_rows; float key_tail_weight;
+} dl_pgca_pairs_probs_args;
+int dl_pgca_pairs_probs(const dl_pgca_pairs_probs_args* a, dl_stream s);
+
+typedef struct {
+  const void* Q; const void* K; float* out;
+  const int32_t* q_index; const int32_t* kv_index;
+  const int64_t* kv_row0; const int32_t* kv_keys; const float* kv_tail_weight; uint32_t* flags;
+  int64_t q_es, q_rs, k_rs, out_ps, out_rs, kv_total_rows;
+  int32_t n_pairs, n_q, n_kv, Lq, head_dim, dtype;
+  int32_t out_cols, expand_tail;
+  float scale;
+  int32_t key_tail_rows;
+} dl_pgca_pairs_ragged_probs_args;
+int dl_pgca_pairs_ragged_probs(const dl_pgca_pairs_ragged_probs_args* a, dl_stream s);
+
 
 /* ------------------------------------------------------------------------------------------
  * MHLA token gate (MultiHeadLinearAttention.forward, model/PMMA/encoder.py:127-140):
@@ -516,7 +582,9 @@ int dl_embed_pad(const int64_t* ids, const void* weight, const void* fill, void*
  * the compact forms below are only valid for inputs with the padding structure of the reference's collate. */
 enum { DL_FLAG_PROT_PERIOD = 1, DL_FLAG_DRUG_TOKEN_PAD = 2, DL_FLAG_GCN_NODE_PAD = 4, DL_FLAG_PLAN_ROWS = 8,
        DL_FLAG_PAIR_INDEX = 16 /* dl_pgca_pairs_fwd: a pair's entity index is out of range (the pair was skipped) */,
-       DL_FLAG_KEY_TABLE = 32 /* dl_pgca_pairs_ragged_fwd: a drug's key table entry is malformed (the pair was skipped) */ };
+       DL_FLAG_KEY_TABLE = 32 /* dl_pgca_pairs_ragged_fwd: a drug's key table entry is malformed (the pair was skipped) */,
+       DL_FLAG_MAP_COLS = 64 /* dl_pgca_pairs_probs / _ragged_probs: a drug's map does not fit out_cols, or expand_tail met a
+                                multiplicity that is no whole number <= 2^24 (the pair was skipped) */ };
 /* ProteinCNN head on distinct rows (round 4; model/basic_model.py:168-171 over a sequence tiled by utils.py:392-412):
  * out[r][:D] = weight[ids[src[r]]], out[r][D] = fill[src[r]] for src[r] >= 0 (a flat index into ids / fill [B * L]), a zero
  * row for src[r] < 0.  weight padded to [V][D + 1] as for dl_embed_pad.  With `period` [B] given the same launch checks
