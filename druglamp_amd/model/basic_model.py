@@ -591,15 +591,45 @@ class DrugLAMPBase(nn.Module):
                                                key_tail_rows=screening.LIB_TAIL_ROWS, cols=n, expand_tail=True)
         return self._pair_maps("cross_attn_prob_library", pcode, lib, "library", pi, di, branch, maps)
 
-    def _pair_maps(self, who, pcode, dcode, dwhat, pi, di, branch, maps) -> torch.Tensor:
+    def _pair_maps(self, who, pcode, dcode, dwhat, pi, di, branch, maps, empty=None):
+        """The branch check, _check_pairs and the index upload in front of a pair-indexed map or profile launch; empty(q): what no
+        pair gives (default: an empty map)."""
         if branch not in ("v", "x") or (branch == "x" and not self.llm_branch):
             raise ValueError("%s: unknown branch %r (this model has %s)" % (who, branch, "'v' and 'x'" if self.llm_branch else "'v'"))
         pi_t, di_t = self._check_pairs(who, pcode, dcode, dwhat, pi, di)
         q = pcode.branches[branch][1]
         if pi_t.numel() == 0:
-            return torch.zeros((0, q.shape[1], 0), dtype=torch.float32, device=q.device)
+            return empty(q) if empty else torch.zeros((0, q.shape[1], 0), dtype=torch.float32, device=q.device)
         gca = self.v_gca if branch == "v" else self.x_gca
         return maps(gca, q, pi_t.to(torch.int32).to(q.device), di_t.to(torch.int32).to(q.device), di_t)
+
+    @torch.no_grad()
+    def cross_attn_profile_codes(self, pcode, dcode, pi, di, branch="v"):
+        """The hit profiles of the pairs (pi[n], di[n]) of cached codes: what cross_attn_prob_codes' maps reduce to, from ONE
+        ops.pgca_pairs_profile launch that never writes a map.  Returns (key_mass (N, cols) fp32: the share of the protein's
+        attention each drug atom / token receives, the map's mean over the sites; site_peak (N, n_site) fp32: a site's largest
+        probability; site_key (N, n_site) int32: the stored key that receives it) on the device.  The checks are score_codes'."""
+        def profile(gca, q, pi_d, di_d, di_t):
+            d = dcode.branches[branch]
+            return ops.pgca_pairs_profile(q, d.kv, pi_d, di_d, scale=float(gca.head_dim) ** -0.5, key_tail=d.key_tail)
+        return self._pair_maps("cross_attn_profile_codes", pcode, dcode, "code", pi, di, branch, profile, empty=self._no_profiles)
+
+    @torch.no_grad()
+    def cross_attn_profile_library(self, pcode, lib, pi, di, branch="v", cols=None):
+        """cross_attn_profile_codes against a resident screening.DrugLibrary (ONE ops.pgca_pairs_ragged_profile launch).  cols: the
+        columns of key_mass, None = the largest full key count among the drugs named (lib.full_keys: host data, no device sync);
+        behind a drug's own count key_mass is +0.0.  site_key indexes the drug's stored keys (lib.keys(branch)[d] of them)."""
+        def profile(gca, q, pi_d, di_d, di_t):
+            b = lib.branches[branch]
+            n = int(lib.full_keys(branch)[di_t].max()) if cols is None else int(cols)
+            return ops.pgca_pairs_ragged_profile(q, b.rows, b.row0, b.n_keys, b.tail_weight, pi_d, di_d, scale=float(gca.head_dim) ** -0.5,
+                                                 key_tail_rows=screening.LIB_TAIL_ROWS, cols=n)
+        return self._pair_maps("cross_attn_profile_library", pcode, lib, "library", pi, di, branch, profile, empty=self._no_profiles)
+
+    @staticmethod
+    def _no_profiles(q):
+        return (torch.zeros((0, 0), dtype=torch.float32, device=q.device), torch.zeros((0, q.shape[1]), dtype=torch.float32, device=q.device),
+                torch.zeros((0, q.shape[1]), dtype=torch.int32, device=q.device))
 
     def get_cross_attn_mat(self, modality="v"):
         if modality == "v":

@@ -14,8 +14,8 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import (DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, PgcaPairsArgs, PgcaPairsProbsArgs, PgcaPairsRaggedArgs,
-                   PgcaPairsRaggedProbsArgs, check)
+from ._lib import (DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, PgcaPairsArgs, PgcaPairsProbsArgs, PgcaPairsProfileArgs,
+                   PgcaPairsRaggedArgs, PgcaPairsRaggedProbsArgs, PgcaPairsRaggedProfileArgs, check)
 
 _DT = {torch.float32: DL_F32, torch.bfloat16: DL_BF16}
 
@@ -617,6 +617,84 @@ def pgca_pairs_ragged_probs(q, rows, row0, n_keys, tail_weight, q_index, kv_inde
     a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
     a.key_tail_rows = int(key_tail_rows)
     check(_lib.lib().dl_pgca_pairs_ragged_probs(C.byref(a), _stream()), "dl_pgca_pairs_ragged_probs")
+    return out
+
+
+def _pgca_profile_common(who, a, q, store, store_name, store_dims, q_index, kv_index, scale, cols, out):
+    """What pgca_pairs_profile and pgca_pairs_ragged_profile share: the checks of q, of the [K | V'] store and of the index
+    vectors; the outputs (key_mass (n_pairs, cols) fp32, site_peak (n_pairs, Lq) fp32, site_key (n_pairs, Lq) int32), allocated
+    or validated; the fields the two argument blocks have in common.  Returns the three outputs."""
+    _check_pair_operands(who, q, store, store_name, store_dims, q_index, kv_index)
+    cols = int(cols)
+    if cols < 1:
+        raise ValueError("%s: cols %d must be positive" % (who, cols))
+    n_pairs, (n_q, Lq, E) = q_index.numel(), q.shape
+    if out is None:
+        out = (torch.empty((n_pairs, cols), dtype=torch.float32, device=q.device),
+               torch.empty((n_pairs, Lq), dtype=torch.float32, device=q.device),
+               torch.empty((n_pairs, Lq), dtype=torch.int32, device=q.device))
+    else:
+        ok = isinstance(out, (tuple, list)) and len(out) == 3
+        for t, dt, width in zip(out if ok else (), (torch.float32, torch.float32, torch.int32), (cols, Lq, Lq)):
+            ok = ok and (t.dim() == 2 and t.dtype == dt and t.device == q.device and t.shape[0] == n_pairs and t.shape[1] >= width
+                         and t.stride(1) == 1 and t.stride(0) >= width)
+        if not ok or out[1].stride(0) != out[2].stride(0):
+            raise ValueError("%s: out must be (key_mass float32 (%d, >= %d), site_peak float32 (%d, >= %d), site_key int32 (%d, >= %d)) "
+                             "on q's device with contiguous columns, non-overlapping rows and one row pitch for the two site "
+                             "outputs" % (who, n_pairs, cols, n_pairs, Lq, n_pairs, Lq))
+        out = tuple(out)
+    mass, peak, skey = out
+    a.Q, a.K, a.key_mass, a.site_peak, a.site_key = q.data_ptr(), store.data_ptr(), mass.data_ptr(), peak.data_ptr(), skey.data_ptr()
+    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
+    a.q_es, a.q_rs = q.stride(0), q.stride(1)
+    a.k_rs = store.stride(-2)
+    a.mass_ps, a.site_ps = mass.stride(0), peak.stride(0)
+    a.n_pairs, a.n_q, a.Lq, a.head_dim, a.dtype = n_pairs, n_q, Lq, E, _dt(q)
+    a.out_cols = cols
+    a.scale = float(scale)
+    return out
+
+
+def pgca_pairs_profile(q, kv, q_index, kv_index, *, scale, key_tail=None, cols=None, out=None):
+    """Hit profiles of (protein, drug) pairs over cached entity codes (dl_pgca_pairs_profile): the two reductions of the map P
+    that pgca_pairs_probs(expand_tail=True) gives for pair n, from ONE launch that never writes the map.  Returns
+    (key_mass (n_pairs, cols) fp32: the mean of P over the query rows, the share of the protein's attention each drug key
+    receives, +0.0 behind the drug's full key count; site_peak (n_pairs, Lq) fp32: a row's largest probability; site_key
+    (n_pairs, Lq) int32: the stored key that receives it — the smallest column attaining the maximum, so a tail key is named by
+    its copy 0 and competes with ONE copy's probability).  q, kv, key_tail, cols as in pgca_pairs_probs (the weight must be
+    whole; kv of at most 576 keys).  out: the three tensors to write into (rows may be wider; the two site outputs share one
+    pitch).  A pair with an index out of range is skipped and sets FLAG_PAIR_INDEX in the device guard word."""
+    _need_gpu(q, kv, q_index, kv_index, *(out if isinstance(out, (tuple, list)) else ()))
+    a = PgcaPairsProfileArgs()
+    t, w = (int(key_tail[0]), float(key_tail[1])) if key_tail is not None else (0, 1.0)
+    if cols is None and kv.dim() == 3:
+        cols = kv.shape[1] - t + t * int(w) if t else kv.shape[1]
+    out = _pgca_profile_common("pgca_pairs_profile", a, q, kv, "kv", ("n_kv", "Lk"), q_index, kv_index, scale, cols or 0, out)
+    a.k_es = kv.stride(0)
+    a.n_kv, a.Lk = kv.shape[:2]
+    if key_tail is not None:
+        a.key_tail_rows, a.key_tail_weight = t, w
+    check(_lib.lib().dl_pgca_pairs_profile(C.byref(a), _stream()), "dl_pgca_pairs_profile")
+    return out
+
+
+def pgca_pairs_ragged_profile(q, rows, row0, n_keys, tail_weight, q_index, kv_index, *, scale, key_tail_rows, cols, out=None):
+    """pgca_pairs_profile over a packed per-drug row store (dl_pgca_pairs_ragged_profile; screening.DrugLibrary): the key table
+    is pgca_pairs_ragged's, the profile that of the drug's map over its full key set (n_keys[d] - key_tail_rows + key_tail_rows *
+    tail_weight[d] columns of `cols`).  A pair is skipped — none of the three outputs is written for it — and flagged in the
+    device guard word (check_guard_flags) when its index is out of range (FLAG_PAIR_INDEX), its drug's table entry does not
+    describe rows inside `rows` (FLAG_KEY_TABLE), or its map has more than `cols` columns, its weight is not whole or it has
+    more than 576 stored keys (FLAG_MAP_COLS)."""
+    _need_gpu(q, rows, row0, n_keys, tail_weight, q_index, kv_index, *(out if isinstance(out, (tuple, list)) else ()))
+    _check_key_table("pgca_pairs_ragged_profile", q, row0, n_keys, tail_weight)
+    if int(key_tail_rows) < 0:
+        raise ValueError("pgca_pairs_ragged_profile: key_tail_rows %d is negative" % int(key_tail_rows))
+    a = PgcaPairsRaggedProfileArgs()
+    out = _pgca_profile_common("pgca_pairs_ragged_profile", a, q, rows, "rows", ("R",), q_index, kv_index, scale, cols, out)
+    a.kv_row0, a.kv_keys, a.kv_tail_weight = row0.data_ptr(), n_keys.data_ptr(), tail_weight.data_ptr()
+    a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
+    a.key_tail_rows = int(key_tail_rows)
+    check(_lib.lib().dl_pgca_pairs_ragged_profile(C.byref(a), _stream()), "dl_pgca_pairs_ragged_profile")
     return out
 
 

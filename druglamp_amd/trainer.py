@@ -23,6 +23,7 @@ What is new (MI355X-native):
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 from typing import Dict, List, Optional, Sequence
@@ -33,6 +34,9 @@ import torch.distributed as dist
 from . import functional as Fn
 from . import ops
 from .model.basic_model import binary_cross_entropy, cross_entropy_logits
+
+# Trainer.hit_profiles: key_mass (P, k, cols) fp32, site_peak (P, k, n_site) fp32, site_key (P, k, n_site) int32, on the CPU
+HitProfiles = collections.namedtuple("HitProfiles", "key_mass site_peak site_key")
 
 
 class CosineAnnealingWarmupRestarts:
@@ -1055,39 +1059,66 @@ class Trainer:
         streamed as in screen_library (the same ones, in the same order); the maps come straight from the cached codes
         (model.cross_attn_prob_library), pair_batch pairs at a time, each chunk copied to the host: device memory holds
         O(pair_batch) maps whatever P and k."""
+        P, k, cols, outs = self._hit_stream("hit_maps", protein_batches, lib, indices, branch, pair_batch,
+                                            lambda pcode, pi, di, cols: (self.model.cross_attn_prob_library(pcode, lib, pi, di, branch=branch, cols=cols),))
+        if outs is None:
+            return torch.zeros((0, k, 0, 0), dtype=torch.float32)
+        return outs[0].view(P, k, outs[0].shape[1], cols)
+
+    @torch.no_grad()
+    def hit_profiles(self, protein_batches, lib, indices, branch: str = "v", pair_batch: int = 256) -> HitProfiles:
+        """The hit profiles of screening hits: what hit_maps' maps reduce to, for every hit of a large screen (about 4 KB per
+        hit where a map is 512 KB; no map is written anywhere).  For protein p and its j-th hit, drug indices[p, j]:
+        key_mass[p, j, c] is the share of the protein's attention that drug key c receives (the map's mean over the sites;
+        cols = the largest full key count among the hits, +0.0 behind a drug's own), site_peak[p, j, r] the largest probability
+        in site r's row and site_key[p, j, r] the stored key of the drug that receives it.  Returns HitProfiles(key_mass
+        (P, k, cols) fp32, site_peak (P, k, n_site) fp32, site_key (P, k, n_site) int32) on the CPU.  The protein batches are
+        streamed and the arguments checked as in hit_maps; the profiles come from model.cross_attn_profile_library, pair_batch
+        pairs per launch."""
+        P, k, cols, outs = self._hit_stream("hit_profiles", protein_batches, lib, indices, branch, pair_batch,
+                                            lambda pcode, pi, di, cols: self.model.cross_attn_profile_library(pcode, lib, pi, di, branch=branch, cols=cols))
+        if outs is None:
+            return HitProfiles(torch.zeros((0, k, 0), dtype=torch.float32), torch.zeros((0, k, 0), dtype=torch.float32),
+                               torch.zeros((0, k, 0), dtype=torch.int32))
+        return HitProfiles(*(o.view(P, k, o.shape[1]) for o in outs))
+
+    def _hit_stream(self, who, protein_batches, lib, indices, branch, pair_batch, fetch):
+        """What hit_maps and hit_profiles share: the checks of their arguments, the streaming of the protein batches and the
+        chunking of the hits.  fetch(pcode, pi, di, cols) gives a chunk's results as a tuple of device tensors whose first
+        dimension is the pair; each is copied to the host behind the chunks before it.  Returns (P, k, cols, the tuple of
+        (P * k, ...) CPU tensors, or None where no protein came)."""
         if pair_batch < 1:
-            raise ValueError("hit_maps: pair_batch must be positive")
+            raise ValueError("%s: pair_batch must be positive" % who)
         if branch not in lib.branches:
-            raise ValueError("hit_maps: unknown branch %r (the library has %s)" % (branch, sorted(lib.branches)))
+            raise ValueError("%s: unknown branch %r (the library has %s)" % (who, branch, sorted(lib.branches)))
         idx = torch.as_tensor(indices, dtype=torch.int64).cpu()
         if idx.dim() != 2:
-            raise ValueError("hit_maps: indices must be (P, k), got %s" % (tuple(idx.shape),))
+            raise ValueError("%s: indices must be (P, k), got %s" % (who, tuple(idx.shape),))
         P, k = idx.shape
         if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= lib.n):
-            raise IndexError("hit_maps: drug index out of range [0, %d)" % lib.n)
+            raise IndexError("%s: drug index out of range [0, %d)" % (who, lib.n))
         cols = int(lib.full_keys(branch)[idx.reshape(-1)].max()) if idx.numel() else 0
         self.model.eval()
-        out, p0 = None, 0
+        outs, p0 = None, 0
         for feat_p, llm_p in protein_batches:
             pcode = self.model.encode_proteins(feat_p, llm_p)
             Pn = pcode.n
             if p0 + Pn > P:
-                raise ValueError("hit_maps: indices has %d rows, the protein batches yield more proteins" % P)
-            if out is None:
-                out = torch.empty((P * k, pcode.branches["v"][1].shape[1], cols), dtype=torch.float32)
+                raise ValueError("%s: indices has %d rows, the protein batches yield more proteins" % (who, P))
             pi = torch.arange(Pn).repeat_interleave(k)
             di = idx[p0:p0 + Pn].reshape(-1)
-            for s in range(0, Pn * k, pair_batch):
-                m = self.model.cross_attn_prob_library(pcode, lib, pi[s:s + pair_batch], di[s:s + pair_batch], branch=branch, cols=cols)
-                out[p0 * k + s:p0 * k + s + m.shape[0]].copy_(m)
+            for s in range(0, max(Pn * k, 1), pair_batch):          # (k == 0: one empty chunk gives the results' shapes)
+                parts = fetch(pcode, pi[s:s + pair_batch], di[s:s + pair_batch], cols)
+                if outs is None:
+                    outs = tuple(torch.empty((P * k,) + tuple(t.shape[1:]), dtype=t.dtype) for t in parts)
+                for o, t in zip(outs, parts):
+                    o[p0 * k + s:p0 * k + s + t.shape[0]].copy_(t)
             p0 += Pn
             del pcode
         if p0 != P:
-            raise ValueError("hit_maps: indices has %d rows, the protein batches yielded %d proteins" % (P, p0))
+            raise ValueError("%s: indices has %d rows, the protein batches yielded %d proteins" % (who, P, p0))
         self.check_device_flags()
-        if out is None:
-            return torch.zeros((0, k, 0, 0), dtype=torch.float32)
-        return out.view(P, k, out.shape[1], cols)
+        return P, k, cols, outs
 
     def evaluate(self, batches) -> Dict[str, float]:
         """Metrics over the union of all ranks' samples (the reference's torchmetrics objects gather their states at

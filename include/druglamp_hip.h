@@ -495,6 +495,64 @@ typedef struct {
 } dl_pgca_pairs_ragged_probs_args;
 int dl_pgca_pairs_ragged_probs(const dl_pgca_pairs_ragged_probs_args* a, dl_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Pair-indexed PGCA hit profiles: the two reductions of a probability map that interpretation asks for
+ * (which drug keys receive a protein's attention; which sites attend sharply, and to what), computed
+ * from the same operands as the maps above WITHOUT writing the map (csrc/pgca_pairs_profile.hip): about
+ * 4 KB per pair instead of 512 KB.  dl_pgca_pairs_profile takes dense codes, dl_pgca_pairs_ragged_profile
+ * the packed row store and its device table, exactly as dl_pgca_pairs_probs / dl_pgca_pairs_ragged_probs do;
+ * both launch one kernel, and on a store of equal-length drugs they give the same bits.
+ *
+ * For pair n < n_pairs with p = q_index[n], d = kv_index[n], let P (Lq rows, F_d = lead_d + t * w_d columns)
+ * be the map the entry points above define under expand_tail == 1 (copy i of tail key j at column
+ * lead_d + i * t + j, every copy carrying exp(scale q.k_{lead_d+j} - LSE_r)):
+ *   key_mass  (n, c) = (1 / Lq) sum_r P[r][c]     c < F_d; +0.0f for F_d <= c < out_cols   (sums to 1 over c)
+ *   site_peak (n, r) = max_c P[r][c]              r < Lq
+ *   site_key  (n, r) = the smallest column at which the computed P[r][.] attains that maximum.  Copies of a
+ *                      tail key are equal and copy 0 comes first, so 0 <= site_key < Lk_d: an index into the
+ *                      drug's STORED keys; a tail key competes with one copy's probability, not w_d times it.
+ * Addressing (element strides; Q / K as above; key_mass and site_peak fp32, site_key int32):
+ *   key_mass  (n, c) = key_mass  + n*mass_ps + c      c < out_cols
+ *   site_peak (n, r) = site_peak + n*site_ps + r      r < Lq       (site_key: the same pitch)
+ * Nothing else is written.  One launch, no workspace, no atomics on data: two calls agree bitwise.
+ * A pair is skipped — nothing is read through its table entry, nothing is written to any of the three
+ * outputs — when
+ *   its index is outside [0, n_q) or [0, n_kv)                                -> DL_FLAG_PAIR_INDEX is OR-ed into *flags
+ *   its table entry is malformed (the conditions of dl_pgca_pairs_ragged_fwd) -> DL_FLAG_KEY_TABLE
+ *   F_d exceeds out_cols, w_d (t > 0) is not a whole number <= 2^24, or the
+ *   drug has more than 576 stored keys                                        -> DL_FLAG_MAP_COLS
+ * (flags may be NULL).  For the dense entry point these are known on the host and checked there (DL_ERR_SHAPE /
+ * DL_ERR_ARG; Lk > 576: DL_ERR_UNSUPPORTED).
+ * One head, head_dim == 128 (else DL_ERR_UNSUPPORTED); Lq arbitrary (one workgroup walks a pair's query blocks);
+ * Q / K 16-byte aligned with strides multiples of 16 bytes; the outputs and index vectors 4-byte, kv_row0 8-byte
+ * aligned; mass_ps >= out_cols > 0, site_ps >= Lq; key_tail_rows >= 0 (dense: <= Lk, key_tail_weight >= 1),
+ * kv_total_rows >= 0; reserved == 0.  n_pairs == 0: DL_OK, nothing is launched, no pointer is looked at.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* Q; const void* K; float* key_mass; float* site_peak; int32_t* site_key;
+  const int32_t* q_index; const int32_t* kv_index; uint32_t* flags;
+  int64_t q_es, q_rs, k_es, k_rs, mass_ps, site_ps;
+  int32_t n_pairs, n_q, n_kv, Lq, Lk, head_dim, dtype;
+  int32_t out_cols;
+  float scale;
+  int32_t key_tail_rows; float key_tail_weight;
+  int32_t reserved;
+} dl_pgca_pairs_profile_args;
+int dl_pgca_pairs_profile(const dl_pgca_pairs_profile_args* a, dl_stream s);
+
+typedef struct {
+  const void* Q; const void* K; float* key_mass; float* site_peak; int32_t* site_key;
+  const int32_t* q_index; const int32_t* kv_index;
+  const int64_t* kv_row0; const int32_t* kv_keys; const float* kv_tail_weight; uint32_t* flags;
+  int64_t q_es, q_rs, k_rs, mass_ps, site_ps, kv_total_rows;
+  int32_t n_pairs, n_q, n_kv, Lq, head_dim, dtype;
+  int32_t out_cols;
+  float scale;
+  int32_t key_tail_rows;
+  int32_t reserved;
+} dl_pgca_pairs_ragged_profile_args;
+int dl_pgca_pairs_ragged_profile(const dl_pgca_pairs_ragged_profile_args* a, dl_stream s);
+
 
 /* ------------------------------------------------------------------------------------------
  * MHLA token gate (MultiHeadLinearAttention.forward, model/PMMA/encoder.py:127-140):
