@@ -914,8 +914,6 @@ class ProteinCNNFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, *_):
         B, LP, C, Lv, training, pool_site_len, raw_dx, n = ctx.cfg
-        if not training:
-            raise RuntimeError("ProteinCNNFn.backward is only implemented for training-mode BatchNorm")
         sv = ctx.saved_tensors
         R = B * LP
         rw = ctx.rw
@@ -938,13 +936,21 @@ class ProteinCNNFn(torch.autograd.Function):
               pl = (k - 1) // 2
               pr = k - 1 - pl
               Mg = R - (k - 1)
-              sums = ops.bn_bwd_reduce(dz, y, mean, rstd, LP, _CNN_HALO, Lv, rw)
-              dpre = ops.bn_bwd_apply(dz, y, mean, rstd, gamma, sums, 1.0 / n, True, LP, _CNN_HALO, Lv, rw)
+              if training:
+                  sums = ops.bn_bwd_reduce(dz, y, mean, rstd, LP, _CNN_HALO, Lv, rw)
+                  dpre = ops.bn_bwd_apply(dz, y, mean, rstd, gamma, sums, 1.0 / n, True, LP, _CNN_HALO, Lv, rw)
+              else:
+                  # BatchNorm on its running statistics: no mean terms, so one pass gives dpre and the sums, and the row
+                  # multiplicities drop out (a representative's dz already is the sum over its positions)
+                  want = ctx.needs_input_grad[8 + i * 6 + 2] or ctx.needs_input_grad[8 + i * 6 + 3]
+                  dpre, sums = ops.bn_eval_bwd(dz, y, mean, rstd, gamma, relu_in=True, win=LP, halo=_CNN_HALO, valid=Lv, row_w=rw,
+                                               want_sums=want)
               # rows outside [pl, pl + Mg) are halo rows (zero in dpre), so the bias gradient can ride along
               dWgs[i], dbias = _wgrad(dpre[pl:pl + Mg], xin, C, k * C, Mg, C, C)
               grads[i * 6 + 1] = dbias
-              grads[i * 6 + 2] = sums[C:]
-              grads[i * 6 + 3] = sums[:C]
+              if sums is not None:
+                  grads[i * 6 + 2] = sums[C:]
+                  grads[i * 6 + 3] = sums[:C]
               if i > 0 or ctx.needs_input_grad[0]:
                   Wd = _conv_weight(w, cdt, True)
                   dprev = torch.empty((R, C), dtype=cdt, device=dout.device)
@@ -1246,6 +1252,33 @@ class SitePoolFn(torch.autograd.Function):
         return ops.cnn_sitepool_bwd(dout, L, 0, site_len), None
 
 
+class FillPoolFn(torch.autograd.Function):
+    """ops.fill_pool for an input that carries a gradient (the input gradient of a deployed model with respect to an LLM
+    embedding): pooled[b, s, f] is the mean of x[b, j * n_site + s, f] over the site_len values of j; the fill bit and the
+    padding columns carry none.  The backward is the transpose of that mean (torch glue: off every training path, where the
+    LLM embeddings are data)."""
+
+    @staticmethod
+    def forward(ctx, x, site_len, out_dtype):
+        ctx.cfg = (tuple(x.shape), x.dtype, int(site_len))
+        fill, pooled = ops.fill_pool(x, site_len, out_dtype)
+        ctx.mark_non_differentiable(fill)
+        return fill, pooled
+
+    @staticmethod
+    def backward(ctx, _dfill, dpooled):
+        (B, S, F), dt, site_len = ctx.cfg
+        d = dpooled[..., :F].to(dt) / site_len                        # (B, n_site, F)
+        return d.unsqueeze(1).expand(B, site_len, S // site_len, F).reshape(B, S, F), None, None
+
+
+def fill_pool(x: torch.Tensor, site_len: int, out_dtype: torch.dtype):
+    """ops.fill_pool; differentiable in x where x asks for a gradient."""
+    if x.requires_grad and torch.is_grad_enabled():
+        return FillPoolFn.apply(x, site_len, out_dtype)
+    return ops.fill_pool(x, site_len, out_dtype)
+
+
 class BatchNormRowsFn(torch.autograd.Function):
     """BatchNorm1d over the rows of a [R][C] matrix (training: batch statistics) on the dl_bn_* kernels.
     Returns (y, mean, var) with biased variance; running-stat bookkeeping stays with the caller."""
@@ -1274,11 +1307,15 @@ class BatchNormRowsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _m, _v):
         x, mean, rstd, g, b = ctx.saved_tensors
-        if not ctx.training:
-            raise RuntimeError("BatchNormRowsFn.backward: eval-mode backward is not implemented")
         R, C = x.shape
         dy = dy.contiguous()
-        if ctx.relu:
+        if not ctx.training:
+            # fixed statistics: dx needs no column sums — one pass gives dx and (d beta | d gamma); all parameters frozen
+            # (the input gradient of a deployed model): the dx pass alone
+            dx, sums = ops.bn_eval_bwd(dy, x, mean, rstd, g, b, relu_out=ctx.relu, want_sums=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+            if sums is None:
+                return dx, None, None, None, None, None, None, None, None
+        elif ctx.relu:
             dx, sums = ops.bn_relu_bwd(dy, x, mean, rstd, g, b, 1.0 / R)
         else:
             sums = ops.bn_bwd_reduce(dy, x, mean, rstd, 0, 0, 0)

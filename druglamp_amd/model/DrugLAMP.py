@@ -25,8 +25,8 @@ class DrugLAMP(DrugLAMPBase):
         # one pass over each LLM tensor: fill bit + (site-pooled) fill-bit-augmented features, already padded
         # to the GEMM alignment (641 -> 648, 385 -> 392 columns)
         cdt = self.compute_dtype
-        fill_p, xps = ops.fill_pool(xp, self.site_len, cdt)
-        fill_d, xdp = ops.fill_pool(xd, 1, cdt)
+        fill_p, xps = Fn.fill_pool(xp, self.site_len, cdt)
+        fill_d, xdp = Fn.fill_pool(xd, 1, cdt)
         # the reference concatenates the fill bits onto the raw tensors here (DrugLAMP.py:11-19); those copies
         # are only consumed by the SSL head, so they are handed over as (tensor, fill bit) pairs and
         # materialised by SSL.forward on SSL epochs only
@@ -70,11 +70,11 @@ class DrugLAMP(DrugLAMPBase):
             vd = self.drug_extractor(vd)
             vdc = Fn.cast(vd, cdt)
             vtail = getattr(vd, "_dl_tail", None)
-        fill_p, xps = ops.fill_pool(xp, self.site_len, cdt)
+        fill_p, xps = Fn.fill_pool(xp, self.site_len, cdt)
         sb.wait_stream(cur)
         with torch.cuda.stream(sb):              # branch b: protein LLM adaptor
             xpc = self._prot_adaptor(xps)
-        fill_d, xdp = ops.fill_pool(xd, 1, cdt)
+        fill_d, xdp = Fn.fill_pool(xd, 1, cdt)
         sc.wait_stream(cur)
         with torch.cuda.stream(sc):              # branch c: drug LLM adaptor
             xdc = self._drug_adaptor(xdp, hints.drug_tokens if hints is not None else 0)

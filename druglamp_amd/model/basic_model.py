@@ -205,14 +205,18 @@ class ProteinCNN(nn.Module):
         params = []
         for conv, bn in ((self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)):
             params += [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        momenta = (self.bn1.momentum, self.bn2.momentum, self.bn3.momentum) if self.training else None
+        # the BatchNorm mode is the BatchNorm modules' own (frozen BatchNorm: they stay in eval inside a training model)
+        bn_training = self.bn1.training
+        if self.bn2.training != bn_training or self.bn3.training != bn_training:
+            raise ValueError("ProteinCNN: bn1 / bn2 / bn3 must all be in training mode or all in eval mode")
+        momenta = (self.bn1.momentum, self.bn2.momentum, self.bn3.momentum) if bn_training else None
         if plan is not None:
             if (plan.B, plan.S) != (B, L):
                 raise ValueError("ProteinCNN: the plan is for a (%d, %d) batch, the ids are (%d, %d)" % (plan.B, plan.S, B, L))
             x = EmbedRowsFn.apply(ids, wc, fill_mask, self.embedding.padding_idx, plan.src, plan.period)     # (R, C) compact rows
             C = x.shape[-1]
-            outs = ProteinCNNFn.apply(x, self.training, self.bn1.eps, 0, momenta, True, plan.w, plan.n, *params)
-            if self.training:
+            outs = ProteinCNNFn.apply(x, bn_training, self.bn1.eps, 0, momenta, True, plan.w, plan.n, *params)
+            if bn_training:
                 for bn in (self.bn1, self.bn2, self.bn3):
                     Fn.bn_tick(bn.num_batches_tracked)
             if site_pool and self.pool_through_map and ops.cnn_sitepool_rows_supported(L, int(site_pool), outs[0].shape[1], outs[0].dtype):
@@ -231,9 +235,9 @@ class ProteinCNN(nn.Module):
         # site pooling (the masked-LM pass of the SSL epochs) that is site_len = 1: the reinterpretation alone, one launch each
         # way (round 5; two 150 MB torch copies per direction before: 0.5 ms of an SSL-epoch step at batch 256)
         fused_pool = (int(site_pool) or 1) if (x.dtype == torch.bfloat16 and L % (int(site_pool) or 1) == 0) else 0
-        outs = ProteinCNNFn.apply(x, self.training, self.bn1.eps, fused_pool, momenta, True, None, 0, *params)
+        outs = ProteinCNNFn.apply(x, bn_training, self.bn1.eps, fused_pool, momenta, True, None, 0, *params)
         z = outs[0]
-        if self.training:
+        if bn_training:
             for bn in (self.bn1, self.bn2, self.bn3):
                 Fn.bn_tick(bn.num_batches_tracked)    # running mean / var were updated inside (dl_bn_finalize)
         if fused_pool:
@@ -355,6 +359,24 @@ class DrugLAMPBase(nn.Module):
         for m in self.modules():
             if isinstance(m, (GuidedCrossAttention, MultiHeadLinearAttention, PairedMultimodelAttention, ProteinCNN, MolecularGCN, SSL, MLP)):
                 m.compute_dtype = dtype
+        return self
+
+    # ---- frozen BatchNorm (fine-tuning at small batches) ----------------------------------------------
+    bn_frozen = False
+
+    def freeze_batchnorm(self, on: bool = True):
+        """on: every nn.BatchNorm1d under the model normalises with its running statistics and leaves them (and its step
+        counter) alone, also through later model.train() calls; its weight / bias keep training.  Dropout and everything else
+        follow train() as before; state_dict is unaffected.  off: the BatchNorm modules follow the model's mode again."""
+        self.bn_frozen = bool(on)
+        return self.train(self.training)
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        if self.bn_frozen:
+            for m in self.modules():
+                if isinstance(m, nn.BatchNorm1d):
+                    m.training = False
         return self
 
     def _glue(self):

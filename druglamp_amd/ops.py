@@ -982,6 +982,26 @@ def bn_relu_bwd(dz2d, y2d, mean, rstd, gamma, beta, inv_n):
     return dy, sums
 
 
+def bn_eval_bwd(dz, y, mean, rstd, gamma, beta=None, *, relu_in=False, relu_out=False, win=0, halo=0, valid=0, row_w=None,
+                want_sums=True):
+    """Backward of a BatchNorm on fixed statistics (eval mode) in one pass (dl_bn_eval_bwd): (dx, sums [2C] = (d beta | d gamma) or
+    None).  relu_out: a ReLU behind the BatchNorm (needs beta); relu_in: y is the output of a ReLU in front of it; row_w < 0
+    marks excluded rows and is otherwise not applied (a compact row's dz already is the sum over the rows it stands for)."""
+    R, Cc = y.shape
+    L = _lib.lib()
+    if relu_out and beta is None:
+        raise ValueError("bn_eval_bwd: relu_out needs beta")
+    dx = torch.empty_like(y)
+    sums = ws = None
+    if want_sums:
+        sums = torch.empty(2 * Cc, dtype=torch.float32, device=y.device)
+        ws = _ws2.get(L.dl_bn_workspace_bytes(R, Cc), y.device)
+    check(L.dl_bn_eval_bwd(dz.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), _ptr(beta) if relu_out else None,
+                           int(relu_in), int(relu_out), dx.data_ptr(), _ptr(sums), R, Cc, int(win), int(halo), int(valid), _ptr(row_w),
+                           _dt(y), _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "dl_bn_eval_bwd")
+    return dx, sums
+
+
 def bn_tail_fix(dy2d, y2d, mean, rstd, gamma, sums, inv_n, w, win, lead):
     """In place: the tail rows of every `win`-row window take the mean terms of the BatchNorm backward w times (dl_bn_tail_fix)."""
     R, Cc = y2d.shape

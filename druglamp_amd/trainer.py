@@ -246,7 +246,8 @@ class GraphedStep:
       * dropout masks are keyed by (site seed + *device offset*): the first node of the graph bumps the offset
         (ops.seed_offset_tensor), forward and backward of one replay read the same value;
       * the weight images are refreshed from the fp32 masters by the dl_weight_prep launch at the head of the graph;
-      * BatchNorm running statistics are updated by the in-graph dl_bn_finalize launches."""
+      * BatchNorm running statistics are updated by the in-graph dl_bn_finalize launches (none with frozen BatchNorm: the
+        flag is part of the trainer's graph key)."""
 
     def __init__(self, trainer: "Trainer", batch, kind: str = "cls", meta=None, caps=None):
         """Capture only records (nothing executes): the caller has already run eager steps of this shape AND kind, so lazy
@@ -448,9 +449,17 @@ class Trainer:
     grad_bf16 = False
     graph_allreduce = False
 
-    def __init__(self, model, cfg, device=None, compute_dtype=torch.float32, graph_steps: bool = False):
+    def __init__(self, model, cfg, device=None, compute_dtype=torch.float32, graph_steps: bool = False, freeze_bn: bool = False):
+        """freeze_bn=True: fine-tuning with frozen BatchNorm (model.freeze_batchnorm()): every BatchNorm1d normalises with its
+        running statistics, which the steps leave bitwise unchanged; its weight / bias train.  cls steps only (eager or
+        replayed): with the SSL or the CM head switched on (RS.SSL / RS.CM) construction raises."""
         self.model = model
         self.cfg = cfg
+        if freeze_bn:
+            if bool(cfg["RS"]["SSL"]) or bool(cfg["RS"]["CM"]):
+                raise ValueError("Trainer(freeze_bn=True) runs cls steps only: the SSL and CM step kinds are not supported with "
+                                 "frozen BatchNorm (set RS.SSL and RS.CM to False)")
+            model.freeze_batchnorm()
         self.device = device or next(model.parameters()).device
         self.n_class = cfg["DECODER"]["BINARY"]
         self.epochs = cfg["SOLVER"]["MAX_EPOCH"]
@@ -756,7 +765,8 @@ class Trainer:
                 (not compute_ssl or ssl_masks is None):
             kind = (("ssl" if compute_ssl else "") + ("cm" if compute_cm else "")) or "cls"
             byval = (float(m.cm_model.m_sch_loss_fn.margin), float(self.cm_weight)) if compute_cm else ()
-            base = (kind,) + GraphedStep.signature(batch) + byval
+            # (frozen BatchNorm is by-value knowledge of a capture too: such a graph has no statistics launches)
+            base = (kind,) + (("frozen_bn",) if getattr(m, "bn_frozen", False) else ()) + GraphedStep.signature(batch) + byval
             # (must_pay=False for the LOOKUP: a batch whose compact layout would not pay on its own still fits — and replays —
             #  a graph that holds tables of its size; GraphedStep.run builds its spec the same way)
             spec_any = self.protein_plan_of(meta, batch, must_pay=False)

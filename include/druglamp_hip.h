@@ -222,6 +222,22 @@ int dl_bn_apply_relu_fwd(const void* y, void* z, const float* mean, const float*
 int dl_bn_relu_bwd(const void* dz, const void* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
                    float inv_n, void* dy, float* sums, int64_t R, int64_t C, int32_t dtype, void* workspace, size_t workspace_bytes,
                    dl_stream s);
+/* Backward of a BatchNorm that ran on fixed statistics (eval mode: mean / rstd from the running statistics; frozen-BatchNorm
+ * fine-tuning and input gradients of a deployed model).  dx does not depend on the column sums, so this is ONE pass over dz
+ * and y plus the second stage over the per-workgroup partials:
+ *   yhat = (y - mean) rstd;  g = dz, counted only where yhat gamma + beta > 0 when relu_out (a ReLU behind the BatchNorm);
+ *   dy = g gamma rstd, zero where y <= 0 when relu_in (y is the output of the ReLU in front of the BatchNorm);
+ *   sums[0..C) = sum g (d beta), sums[C..2C) = sum g yhat (d gamma) over the rows that take part.
+ * Rows: the window rule (win, halo, valid; win = 0: every row), or row_w [R] when given: row_w[r] < 0 excludes the row.  The
+ * weight is otherwise not applied: a compact row's dz already is the sum over the rows it stands for and yhat is shared by
+ * them, so the unweighted sum over the compact rows is the sum over the expanded ones.  Excluded rows of dz and y are never
+ * read; their dy rows are written as +0.  beta is read only with relu_out (else may be NULL).  sums may be NULL: the dy pass
+ * alone, no workspace.  Otherwise workspace: dl_bn_workspace_bytes(R, C); the sums are deterministic (fixed order, no atomics).
+ * dy must not alias dz or y.  bf16 with C in {64, 128, 256} and 16-byte bases takes the 16-byte form, everything else the
+ * generic one. */
+int dl_bn_eval_bwd(const void* dz, const void* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                   int32_t relu_in, int32_t relu_out, void* dy, float* sums, int64_t R, int64_t C, int64_t win, int64_t halo,
+                   int64_t valid, const float* row_w, int32_t dtype, void* workspace, size_t workspace_bytes, dl_stream s);
 
 /* ------------------------------------------------------------------------------------------
  * LayerNorm over the last dim (eps 1e-6 inside PMMA: model/PMMA/block.py:23-27,
