@@ -290,9 +290,10 @@ template <typename T> __device__ __forceinline__ f32x4 gelu4(f32x4 v) {
     return f32x4{ga[0], ga[1], gb[0], gb[1]};
   }
 }
-// gelu'(x) - 1/2 is odd; on |x| <= 5.5 it is x * P(x^2) / Q(x^2) with P cubic and Q cubic in x^2 to 1.0e-4 absolute
-// (least-squares fit, checked in fp32 arithmetic over [-9, 9]) — a factor 40 below the bf16 rounding of the product it
-// feeds.  One reciprocal and 8 packed FMAs per pair instead of erf + exp (the gelu' data-gradient epilogue is VALU-bound).
+// gelu'(x) - 1/2 is odd; on |x| <= 5.5 it is x * P(x^2) / Q(x^2) with P cubic and Q cubic in x^2 to 1.02e-4 absolute
+// (least-squares fit; measured in fp32 arithmetic on 2.4 million points over [-12, 12]: worst 1.013e-4 at |x| = 0.282,
+// tests/test_elem_reference_cpu.py) — a factor 40 below the bf16 rounding of the product it feeds.  One reciprocal and
+// 8 packed FMAs per pair instead of erf + exp (the gelu' data-gradient epilogue is VALU-bound).
 __device__ __forceinline__ f32x2 gelu_grad_fast2(f32x2 x) {
   x = f32x2{__builtin_amdgcn_fmed3f(x[0], -5.5f, 5.5f), __builtin_amdgcn_fmed3f(x[1], -5.5f, 5.5f)};   // (v_med3_f32: one slot per element; min + max: two)
   const f32x2 x2 = x * x;
@@ -320,6 +321,9 @@ template <typename T> __device__ __forceinline__ f32x4 gelu_grad4(f32x4 v) {
 // elements (16 bits each).  keep[j] = bits16[j] >= thr16 with thr16 = round(p * 65536).  Two murmur3
 // finalisers on decorrelated 32-bit keys (4 integer multiplies per 4 elements); the mask is regenerated
 // from the same (seed, index) in backward, never stored.
+// thr16 == 0 (p == 0, or 0 < p < 2^-17) means NO dropout at that site: no draw, nothing dropped, no 1 / (1 - p) scaling.
+// The hosts of the forward kernels (dl_add_rowmod_dropout, the GEMM epilogues) skip the dropout step on thr16 == 0 and
+// dl_dropout_apply, which replays a site in backward, copies with scale 1, so forward and backward agree.
 __device__ __forceinline__ uint32_t dl_fmix32(uint32_t h) {
   h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
   return h;

@@ -413,8 +413,8 @@ __global__ __launch_bounds__(256) void norm_adj_kernel(const float* __restrict__
   }
 }
 
-// the same for graphs whose fp32 tile does not fit LDS (n > 190): degrees first (only they live in LDS), the adjacency
-// is read from global memory / L2 twice
+// the same for graphs whose fp32 tile does not fit the 150 KB of LDS the host allows (n >= 195; n <= 194 takes the form
+// above): degrees first (only they live in LDS), the adjacency is read from global memory / L2 twice
 template <typename TO>
 __global__ __launch_bounds__(256) void norm_adj_any_kernel(const float* __restrict__ adj, TO* __restrict__ ahat, int n) {
   extern __shared__ __attribute__((aligned(16))) char na_smem[];
@@ -748,13 +748,17 @@ extern "C" int dl_dropout_apply(const void* x, void* y, int64_t n_rows, int64_t 
   DL_CHECK_ARG(x && y && n_rows > 0 && D > 0 && D % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, DL_ERR_ARG,
                "dl_dropout_apply: bad args");
   DL_CHECK_ARG(p > 0.f && p < 1.f, DL_ERR_ARG, "dl_dropout_apply: p must be in (0,1)");
+  // thr16 == 0 (p < 2^-17) is no dropout by the contract of common.cuh: every element kept, scale 1 (a plain copy), as the
+  // forward kernels (dl_add_rowmod_dropout, the GEMM epilogues) leave such a site untouched
+  const uint32_t thr = dl_dropout_thr16(p);
+  const float inv = thr ? 1.0f / (1.0f - p) : 1.0f;
   const int64_t n4 = n_rows * D / 4;
   if (dtype == DL_BF16)
     hipLaunchKernelGGL((dropout_apply_kernel<bf16_t>), dim3(nblk(n4)), dim3(256), 0, s, (const bf16_t*)x,
-                       (bf16_t*)y, n_rows, (int)D, ldx, ldy, dl_dropout_thr16(p), 1.0f / (1.0f - p), seed, seed_offset);
+                       (bf16_t*)y, n_rows, (int)D, ldx, ldy, thr, inv, seed, seed_offset);
   else
     hipLaunchKernelGGL((dropout_apply_kernel<float>), dim3(nblk(n4)), dim3(256), 0, s, (const float*)x, (float*)y,
-                       n_rows, (int)D, ldx, ldy, dl_dropout_thr16(p), 1.0f / (1.0f - p), seed, seed_offset);
+                       n_rows, (int)D, ldx, ldy, thr, inv, seed, seed_offset);
   DL_CHECK_LAUNCH("dl_dropout_apply");
   return DL_OK;
 }
@@ -858,7 +862,7 @@ extern "C" int dl_norm_adjacency(const float* adj, void* ahat, int64_t B, int32_
   DL_CHECK_ARG(adj && ahat && B > 0 && n > 0, DL_ERR_ARG, "dl_norm_adjacency: bad args");
   const size_t lds = ((size_t)n * (n + 1) + 2 * (size_t)n) * sizeof(float);
   DL_CHECK_ARG(n <= 4096, DL_ERR_SHAPE, "dl_norm_adjacency: n=%d (at most 4096 nodes per graph)", n);
-  if (lds > 150 * 1024) {                                     // n > 190: the tile does not fit LDS
+  if (lds > 150 * 1024) {                                     // n >= 195 (n^2 + 3n > 38400): the tile does not fit LDS
     const size_t dl = 2 * (size_t)n * sizeof(float);
     if (out_dtype == DL_BF16) hipLaunchKernelGGL((norm_adj_any_kernel<bf16_t>), dim3((uint32_t)B), dim3(256), dl, s, adj, (bf16_t*)ahat, (int)n);
     else if (out_dtype == DL_F32) hipLaunchKernelGGL((norm_adj_any_kernel<float>), dim3((uint32_t)B), dim3(256), dl, s, adj, (float*)ahat, (int)n);
@@ -919,7 +923,8 @@ extern "C" int dl_embed_pad(const int64_t* ids, const void* weight, const void* 
                             int32_t V, int32_t D, int32_t halo, int32_t dtype, dl_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   DL_CHECK_ARG(ids && weight && fill && out && B > 0 && L > 0 && V > 0 && D > 0 && halo >= 0, DL_ERR_ARG, "dl_embed_pad: bad args");
-  DL_CHECK_ARG((D + 1) % 8 == 0 && (size_t)V * D * dl_dtype_size(dtype) <= 64 * 1024, DL_ERR_SHAPE,
+  // the LDS table holds the PADDED rows [V][D + 1] (what the launch below requests, and what dl_embed_rows checks)
+  DL_CHECK_ARG((D + 1) % 8 == 0 && (size_t)V * (D + 1) * dl_dtype_size(dtype) <= 64 * 1024, DL_ERR_SHAPE,
                "dl_embed_pad: needs (D + 1) %% 8 == 0 and a table that fits 64 KB of LDS");
   DL_CHECK_ARG(B <= 65535, DL_ERR_SHAPE, "dl_embed_pad: B must fit a grid dimension");
   const int64_t per_sample = (L + 2 * halo) * ((D + 1) / 8);

@@ -599,7 +599,7 @@ int dl_interleave_streams(const void* src, void* dst, int64_t R, int64_t row_byt
                           dl_stream s);
 /* Symmetric-normalised, transposed adjacency of a batch of dense graphs: ahat[b][i][j] = din[i] * adj[b][j][i] * dout[j]
  * with clamped degrees^-1/2 (MolecularGCN: model/basic_model.py:137-153, 591-617 — dgl GraphConv norm='both').
- * adj (B, n, n) fp32, ahat (B, n, n) out_dtype; n <= 190. */
+ * adj (B, n, n) fp32, ahat (B, n, n) out_dtype; n <= 4096 (the adjacency tile sits in LDS up to n = 194). */
 int dl_norm_adjacency(const float* adj, void* ahat, int64_t B, int32_t n, int32_t out_dtype, dl_stream s);
 /* Neighbourhood aggregation of MolecularGCN on dense batched graphs (dgl GraphConv norm='both' `update_all(copy_u, sum)`,
  * model/basic_model.py:591-617): out[b][i][:] = sum_j A'[b][i][j] * feat[b][j][:] for the n real nodes (A' = ahat, or
@@ -615,7 +615,8 @@ int dl_concat2(void* a, void* b, void* cat, int64_t R, int64_t a_row_bytes, int6
 /* ------------------------------------------------------------------------------------------
  * Elementwise helpers on the path.
  * ------------------------------------------------------------------------------------------ */
-/* y = dropout(x + pe[row % L]) — Embeddings.forward prot branch (model/PMMA/embed.py:51-52). */
+/* y = dropout(x + pe[row % L]) — Embeddings.forward prot branch (model/PMMA/embed.py:51-52).  A p that rounds to a 16-bit
+ * threshold of 0 (p == 0 or p < 2^-17) is no dropout: the plain sum, unscaled; dl_dropout_apply and dl_gemm do the same. */
 int dl_add_rowmod_dropout(const void* x, const void* pe, void* y, int64_t M, int64_t D,
                           int64_t L, float p, uint64_t seed, const uint64_t* seed_offset, int32_t dtype, dl_stream s);
 /* y = dropout_mask(seed)(x) / (1-p) — regenerates a forward mask for the backward pass.
@@ -649,7 +650,8 @@ int dl_gather_pad(const void* store, const int64_t* offsets, const int32_t* leng
 /* ProteinCNN head (model/basic_model.py:168-171): out[b][halo + l][:D] = weight[ids[b][l]][:] (nn.Embedding row
  * gather), out[b][halo + l][D] = fill[b][l] (the concatenated fill bit); `halo` zero rows on each side of every
  * sample are the conv 'same' padding of this library's channel-last layout.  weight is passed PADDED to
- * [V][D + 1] (last column ignored; 16-byte aligned rows); fill [B][L] and out [B][L + 2*halo][D + 1]; all `dtype`. */
+ * [V][D + 1] (last column ignored; 16-byte aligned rows; the padded table must fit 64 KB of LDS, else DL_ERR_SHAPE);
+ * fill [B][L] and out [B][L + 2*halo][D + 1]; all `dtype`. */
 int dl_embed_pad(const int64_t* ids, const void* weight, const void* fill, void* out, int64_t B, int64_t L,
                  int32_t V, int32_t D, int32_t halo, int32_t dtype, dl_stream s);
 /* Device-side guard flags (sticky bits OR-ed into a caller-owned uint32 word; the trainer polls it):

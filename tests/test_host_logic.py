@@ -192,6 +192,19 @@ def test_c_abi_argument_validation_without_gpu():
     assert L.dl_adamw_step(p16, p16, p16, p16, 16, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 0, 1.0, None, 0, None) == -1
 
 
+def test_embed_pad_checks_the_lds_table_it_requests():
+    """dl_embed_pad stages the PADDED table [V][D + 1] in dynamic LDS without raising the 64 KB limit: fp32, V = 129, D = 127 is
+    65532 bytes unpadded but 66048 padded, and is an argument error returned before any launch (dl_embed_rows checks the same)."""
+    import ctypes as C
+    from druglamp_amd import _lib
+    L = _lib.lib()
+    buf = (C.c_char * 4096)()
+    p16 = (C.addressof(buf) + 15) // 16 * 16
+    assert 129 * 127 * 4 <= 64 * 1024 < 129 * 128 * 4
+    assert L.dl_embed_pad(p16, p16, p16, p16, 1, 8, 129, 127, 0, _lib.DL_F32, None) == -2 and b"LDS" in L.dl_last_error()
+    assert L.dl_embed_rows(p16, p16, p16, p16, p16, 8, 129, 127, None, 0, 0, None, _lib.DL_F32, None) == -2
+
+
 def test_gemm_group_plan_without_gpu():
     """dl_gemm_group_plan is host logic: which groups of weight-gradient products the library takes, and the slab count per
     member (one common count so that tiles x slabs is about one round of 256 workgroups, at least eight 64-row k-steps per
