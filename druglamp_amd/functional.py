@@ -397,6 +397,10 @@ class LinearFn(torch.autograd.Function):
         M = x2.shape[0]
         w = lowp((weight,), cdt)
         wT = lowp((weight,), cdt, transpose=True) if (ctx.needs_input_grad[0] and cdt == torch.bfloat16 and N % 8 == 0) else None   # (K-contiguous data gradient)
+        # an output width that is no whole 16-byte chunk (N % 8 in bf16, N % 4 in fp32): dy's row pitch cannot feed the backward's
+        # GEMMs (dl_gemm refuses ldx = N), so they run on a zero-padded copy of dy and this zero-padded [Np][K] image
+        epc = 16 // x.element_size()
+        wp = lowp((weight,), cdt, pad=((N + epc - 1) // epc * epc, K)) if (ctx.needs_input_grad[0] and N % epc != 0) else None
         p_eff = float(p_drop) if (training and p_drop > 0) else 0.0
         seed = ops.next_seed() if p_eff > 0 else 0
         if pe is None:
@@ -405,23 +409,35 @@ class LinearFn(torch.autograd.Function):
             pe2 = lowp((pe,), cdt).reshape(-1, N)
             y = ops.gemm(x2, w, M=M, N=N, K=K, bias=_f32(bias), residual=pe2, res_row_mod=pe2.shape[0],
                          res_before_dropout=True, dropout_p=p_eff, seed=seed)
-        ctx.save_for_backward(x2, w, wT)
+        ctx.save_for_backward(x2, w, wT, wp)
         ctx.cfg = (x.shape, M, N, K, p_eff, seed, bias is not None, None if pe is None else tuple(pe.shape))
         return y.reshape(*x.shape[:-1], N)
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w, wT = ctx.saved_tensors
+        x2, w, wT, wp = ctx.saved_tensors
         xshape, M, N, K, p_eff, seed, has_bias, pe_shape = ctx.cfg
         g = dy.reshape(M, N).contiguous()
         if p_eff > 0:
             g = ops.dropout_apply(g, p_eff, seed)
+        # (dl_dropout_apply and dl_colsum take any row pitch, dl_rowmod_sum any N % 4 == 0; only the GEMMs need whole chunks)
+        gp, Np, epc = g, N, 16 // g.element_size()
+        if N % epc != 0 and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            Np = (N + epc - 1) // epc * epc
+            gp = torch.zeros((M, Np), dtype=g.dtype, device=g.device)
+            gp[:, :N] = g
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = (ops.gemm(g, wT, M=M, N=K, K=N) if wT is not None else ops.gemm(g, w, M=M, N=K, K=N, w_kslow=True, ldw=K)).reshape(xshape)
+            if wT is not None:
+                dx = ops.gemm(g, wT, M=M, N=K, K=N)
+            else:
+                dx = ops.gemm(gp, w if wp is None else wp, M=M, N=K, K=Np, w_kslow=True, ldw=K)
+            dx = dx.reshape(xshape)
         want_b = has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
-            dw, db = _wgrad(g, x2, N, K, M, N, K, want_bias=want_b)
+            dw, db = _wgrad(gp, x2, Np, K, M, Np, K, want_bias=want_b)
+            if Np != N:
+                dw, db = dw[:N], (db[:N] if want_b else None)
         else:
             dw, db = None, (ops.colsum(g) if want_b else None)
         dpe = None
@@ -604,7 +620,17 @@ class TokenGateFn(torch.autograd.Function):
         cdt = v2.dtype
         dv_gate, dlogits = ops.token_gate_bwd(dout.contiguous(), v2.reshape(B, L, D), gate, H, add_residual)
         dl2 = dlogits.reshape(M, H)
-        dw2, db2 = _wgrad(dl2, hid, H, dd, M, H, dd)
+        # a head count that is no whole 16-byte chunk (H % 8 in bf16, H % 4 in fp32): dl_gemm refuses a row pitch of H, so lin2's
+        # weight gradient and the K-slow data gradient below run on a zero-padded copy of dlogits
+        epc = 16 // dl2.element_size()
+        Hp = (H + epc - 1) // epc * epc
+        dl2w = dl2
+        if Hp != H:
+            dl2w = torch.zeros((M, Hp), dtype=cdt, device=dl2.device)
+            dl2w[:, :H] = dl2
+        dw2, db2 = _wgrad(dl2w, hid, Hp, dd, M, Hp, dd)
+        if Hp != H:
+            dw2, db2 = dw2[:H], db2[:H]
         if GATE_DPRE_KERNEL and H == 8 and dd % 8 == 0 and dd <= 2048 and dl2.is_contiguous():
             # an inner dimension of 8: one elementwise pass (dl_gate_dpre) — rounds 1-4 zero-padded it to a 64-deep k-step for
             # dl_gemm's gelu' epilogue: 77 us + 46 us of padding launches per MHLA block at batch 256
@@ -615,7 +641,8 @@ class TokenGateFn(torch.autograd.Function):
             w2t = lowp((ctx.w2,), cdt, transpose=True, pad=(64, dd))           # [dd][64] image of W2^T
             dpre = ops.gemm(dl2p, w2t, M=M, N=dd, K=64, dact_pre=pre)
         else:
-            dpre = ops.gemm(dl2, lw2, M=M, N=dd, K=H, w_kslow=True, ldw=dd, dact_pre=pre)
+            lw2p = lw2 if Hp == H else lowp((ctx.w2,), cdt, pad=(Hp, dd))
+            dpre = ops.gemm(dl2w, lw2p, M=M, N=dd, K=Hp, w_kslow=True, ldw=dd, dact_pre=pre)
         dw1, db1 = _wgrad(dpre, v2, dd, D, M, dd, D)
         dv = ops.gemm(dpre, lowp((ctx.w1,), cdt, transpose=True), M=M, N=D, K=dd, residual=dv_gate.reshape(M, D))
         return dv.reshape(B, L, D), dw1, db1, dw2, db2, None, None
@@ -892,7 +919,7 @@ class ProteinCNNFn(torch.autograd.Function):
                 mean, var = rmean.detach().float(), rvar.detach().float()
                 rstd = torch.rsqrt(var + eps)
             z = ops.bn_apply_fwd(y, mean, rstd, gamma.detach().float(), beta.detach().float(), LP, _CNN_HALO, Lv, rw)
-            saved += [cur, y, mean, rstd, gamma.detach().float()]
+            saved += [cur, y, mean, rstd, gamma.detach().float()]      # (five per layer, y second: tests/test_functional_paths_gpu.py reads y > 0 there)
             stats_out += [mean, var]
             meta.append((k, pl, w))
             cur = z
