@@ -199,6 +199,35 @@ class PgcaPairsRaggedProfileArgs(C.Structure):
     ]
 
 
+class PgcaPairsAttrArgs(C.Structure):
+    _fields_ = [
+        ("Q", c_vp), ("K", c_vp), ("dO", c_vp), ("sites", c_vp), ("d_sites", c_vp), ("key_attr", c_vp), ("site_attr", c_vp),
+        ("q_index", c_vp), ("kv_index", c_vp), ("flags", c_vp),
+        ("q_es", c_i64), ("q_rs", c_i64), ("k_es", c_i64), ("k_rs", c_i64), ("do_ps", c_i64), ("do_rs", c_i64),
+        ("left_es", c_i64), ("left_rs", c_i64), ("dl_ps", c_i64), ("dl_rs", c_i64), ("mass_ps", c_i64), ("site_ps", c_i64),
+        ("n_pairs", c_i32), ("n_q", c_i32), ("n_kv", c_i32), ("Lq", c_i32), ("Lk", c_i32), ("head_dim", c_i32), ("dtype", c_i32),
+        ("out_cols", c_i32), ("left_cols", c_i32),
+        ("scale", c_f32),
+        ("key_tail_rows", c_i32), ("key_tail_weight", c_f32),
+        ("reserved", c_i32),
+    ]
+
+
+class PgcaPairsRaggedAttrArgs(C.Structure):
+    _fields_ = [
+        ("Q", c_vp), ("K", c_vp), ("dO", c_vp), ("sites", c_vp), ("d_sites", c_vp), ("key_attr", c_vp), ("site_attr", c_vp),
+        ("q_index", c_vp), ("kv_index", c_vp), ("kv_row0", c_vp), ("kv_keys", c_vp), ("kv_tail_weight", c_vp), ("flags", c_vp),
+        ("q_es", c_i64), ("q_rs", c_i64), ("k_rs", c_i64), ("do_ps", c_i64), ("do_rs", c_i64),
+        ("left_es", c_i64), ("left_rs", c_i64), ("dl_ps", c_i64), ("dl_rs", c_i64), ("mass_ps", c_i64), ("site_ps", c_i64),
+        ("kv_total_rows", c_i64),
+        ("n_pairs", c_i32), ("n_q", c_i32), ("n_kv", c_i32), ("Lq", c_i32), ("head_dim", c_i32), ("dtype", c_i32),
+        ("out_cols", c_i32), ("left_cols", c_i32),
+        ("scale", c_f32),
+        ("key_tail_rows", c_i32),
+        ("reserved", c_i32),
+    ]
+
+
 class NtxentSide(C.Structure):
     _fields_ = [("q", c_vp), ("k", c_vp), ("n", c_i64), ("gid_offset", c_i64), ("lse", c_vp)]
 
@@ -243,6 +272,8 @@ SIGNATURES = {
     "dl_pgca_pairs_ragged_probs": (c_i32, [C.POINTER(PgcaPairsRaggedProbsArgs), c_vp]),
     "dl_pgca_pairs_profile": (c_i32, [C.POINTER(PgcaPairsProfileArgs), c_vp]),
     "dl_pgca_pairs_ragged_profile": (c_i32, [C.POINTER(PgcaPairsRaggedProfileArgs), c_vp]),
+    "dl_pgca_pairs_attr": (c_i32, [C.POINTER(PgcaPairsAttrArgs), c_vp]),
+    "dl_pgca_pairs_ragged_attr": (c_i32, [C.POINTER(PgcaPairsRaggedAttrArgs), c_vp]),
     "dl_token_gate_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "dl_token_gate_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "dl_gate_dpre": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),

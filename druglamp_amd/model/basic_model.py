@@ -555,18 +555,92 @@ class DrugLAMPBase(nn.Module):
         if N == 0:
             return torch.zeros((0, n_out), dtype=torch.float32, device=dev)
         pi_d, di_d = pi_t.to(torch.int32).to(dev), di_t.to(torch.int32).to(dev)
+        return self._pair_tail(pcode, lambda name, gca: attend(name, gca, pcode.branches[name][1], pcode.branches[name][0], pi_d, di_d))
+
+    def _pair_tail(self, pcode, concat) -> torch.Tensor:
+        """The tail of the pair stage, shared by scoring and attributing: concat(name, gca) gives a branch's (N, n_site, 256)
+        [sites | guided] rows; MHLA + residual, LayerNorm, PMMA, token mean and the classifier follow as in the forward."""
         m = {}
         for name, gca, mhla, norm in (("v", self.v_gca, self.v_mhla, self.v_gca_norm), ("x", self.x_gca, self.x_mhla, self.x_gca_norm)):
             if name not in pcode.branches:
                 continue
-            sites, q = pcode.branches[name]
-            cat = attend(name, gca, q, sites, pi_d, di_d)
-            h = mhla(cat, add_residual=True)
+            h = mhla(concat(name, gca), add_residual=True)
             m[name] = Fn.layer_norm(h, norm.weight, norm.bias, norm.eps)
         f, _, _ = self.pmma(m["x"], m["v"]) if self.llm_branch else self.pmma(m["v"], m["v"])
         with self._glue():
             score = self.mlp_classifier(Fn.TokenMeanFn.apply(f))
         return score.float()
+
+    def attribute_codes(self, pcode, dcode, pi, di, cols=None):
+        """Gradient x code attributions of the pairs (pi[n], di[n]) of cached codes.  The target is the logit whose sigmoid
+        screening reports (score[:, 0] with one output, score[:, 1] - score[:, 0] with two).  Per branch the [sites | guided]
+        concat of score_codes becomes a leaf, ONE backward of the shared tail gives its gradient for all N pairs, and ONE
+        ops.pgca_pairs_attr launch contracts it with the codes.  Returns (logit (N,) fp32, {branch: (key_attr (N, cols) fp32,
+        site_attr (N, n_site) fp32)}) on the device: key_attr per drug key in cross_attn_profile_codes' key_mass columns,
+        site_attr per protein site.  The numbers are gradient x code at the pair-stage interface — the leaves are the cached
+        codes (sites, q, [K | V']), not the raw inputs in front of the encoders — signed, and no probabilities.  cols: the
+        columns of key_attr (an int, or {branch: int}); None = the codes' full key count.  No parameter's .grad is created or
+        changed.  The checks are score_codes'."""
+        def attend(name, gca, q, sites, pi_d, di_d):
+            d = dcode.branches[name]
+            return ops.pgca_pairs(q, d.kv, pi_d, di_d, scale=float(gca.head_dim) ** -0.5, left=sites, bias=d.bias, key_tail=d.key_tail)
+
+        def attr(name, gca, q, sites, d_sites, d_out, pi_d, di_d, di_t, n):
+            d = dcode.branches[name]
+            return ops.pgca_pairs_attr(q, d.kv, d_out, pi_d, di_d, scale=float(gca.head_dim) ** -0.5, key_tail=d.key_tail, cols=n,
+                                       sites=sites, d_sites=d_sites)
+        return self._attribute_pairs("attribute_codes", pcode, dcode, "code", pi, di, cols, attend, attr)
+
+    def attribute_library(self, pcode, lib, pi, di, cols=None):
+        """attribute_codes against a resident screening.DrugLibrary (per branch ONE ops.pgca_pairs_ragged and ONE
+        ops.pgca_pairs_ragged_attr launch around the one tail backward).  cols: None = per branch the largest full key count
+        among the drugs named (lib.full_keys); behind a drug's own count key_attr is +0.0."""
+        def attend(name, gca, q, sites, pi_d, di_d):
+            b = lib.branches[name]
+            return ops.pgca_pairs_ragged(q, b.rows, b.row0, b.n_keys, b.tail_weight, pi_d, di_d, scale=float(gca.head_dim) ** -0.5,
+                                         key_tail_rows=screening.LIB_TAIL_ROWS, left=sites, bias=b.bias)
+
+        def attr(name, gca, q, sites, d_sites, d_out, pi_d, di_d, di_t, n):
+            b = lib.branches[name]
+            n = int(lib.full_keys(name)[di_t].max()) if n is None else n
+            return ops.pgca_pairs_ragged_attr(q, b.rows, b.row0, b.n_keys, b.tail_weight, d_out, pi_d, di_d, scale=float(gca.head_dim) ** -0.5,
+                                              key_tail_rows=screening.LIB_TAIL_ROWS, cols=n, sites=sites, d_sites=d_sites)
+        return self._attribute_pairs("attribute_library", pcode, lib, "library", pi, di, cols, attend, attr)
+
+    def _attribute_pairs(self, who, pcode, dcode, dwhat, pi, di, cols, attend, attr):
+        """The pair stage behind attribute_codes / attribute_library: the checks, attend() per branch under no_grad, the shared
+        tail on leaf concats under enable_grad, one torch.autograd.grad for every branch and pair (pairs are independent in eval
+        mode), attr() per branch on the halves of the concat's gradient (views, no copy)."""
+        pi_t, di_t = self._check_pairs(who, pcode, dcode, dwhat, pi, di)
+        dev = pcode.branches["v"][1].device
+        if pi_t.numel() == 0:
+            z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+            return z(0), {name: (z(0, 0), z(0, q.shape[1])) for name, (_, q) in pcode.branches.items()}
+        pi_d, di_d = pi_t.to(torch.int32).to(dev), di_t.to(torch.int32).to(dev)
+        leaves = {}
+
+        def concat(name, gca):
+            sites, q = pcode.branches[name]
+            with torch.no_grad():
+                cat = attend(name, gca, q, sites, pi_d, di_d)
+            leaves[name] = cat.requires_grad_(True)
+            return leaves[name]
+        with torch.enable_grad():
+            score = self._pair_tail(pcode, concat)
+            target = score[:, 0] if score.shape[1] == 1 else score[:, 1] - score[:, 0]
+            names = list(leaves)
+            grads = torch.autograd.grad(target.sum(), [leaves[k] for k in names])
+        out = {}
+        with torch.no_grad():
+            for name, grad in zip(names, grads):
+                sites, q = pcode.branches[name]
+                lc = sites.shape[2]
+                if grad.stride(-1) != 1:
+                    grad = grad.contiguous()
+                n = cols.get(name) if isinstance(cols, dict) else cols
+                out[name] = attr(name, self.v_gca if name == "v" else self.x_gca, q, sites, grad[..., :lc], grad[..., lc:], pi_d, di_d, di_t,
+                                 None if n is None else int(n))
+        return target.detach(), out
 
     def _check_pairs(self, who, pcode, dcode, dwhat, pi, di):
         """The checks of every call that pairs cached codes (eval mode, compute dtype, parameter epoch, branches, index ranges);

@@ -14,8 +14,9 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import (DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, PgcaPairsArgs, PgcaPairsProbsArgs, PgcaPairsProfileArgs,
-                   PgcaPairsRaggedArgs, PgcaPairsRaggedProbsArgs, PgcaPairsRaggedProfileArgs, check)
+from ._lib import (DL_BF16, DL_F32, AttnBwdArgs, AttnFwdArgs, AttnProbsArgs, GemmArgs, PgcaPairsArgs, PgcaPairsAttrArgs, PgcaPairsProbsArgs,
+                   PgcaPairsProfileArgs, PgcaPairsRaggedArgs, PgcaPairsRaggedAttrArgs, PgcaPairsRaggedProbsArgs, PgcaPairsRaggedProfileArgs,
+                   check)
 
 _DT = {torch.float32: DL_F32, torch.bfloat16: DL_BF16}
 
@@ -695,6 +696,102 @@ def pgca_pairs_ragged_profile(q, rows, row0, n_keys, tail_weight, q_index, kv_in
     a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
     a.key_tail_rows = int(key_tail_rows)
     check(_lib.lib().dl_pgca_pairs_ragged_profile(C.byref(a), _stream()), "dl_pgca_pairs_ragged_profile")
+    return out
+
+
+def _pgca_attr_common(who, a, q, store, store_name, store_dims, d_out, q_index, kv_index, scale, cols, sites, d_sites, out):
+    """What pgca_pairs_attr and pgca_pairs_ragged_attr share: the checks of q, of the [K | V'] store, of the index vectors, of
+    d_out and of sites / d_sites; the outputs (key_attr (n_pairs, cols) fp32, site_attr (n_pairs, Lq) fp32), allocated or
+    validated; the fields the two argument blocks have in common.  Returns the two outputs."""
+    _check_pair_operands(who, q, store, store_name, store_dims, q_index, kv_index)
+    cols = int(cols)
+    if cols < 1:
+        raise ValueError("%s: cols %d must be positive" % (who, cols))
+    n_pairs, (n_q, Lq, E) = q_index.numel(), q.shape
+    if d_out.dtype != q.dtype:
+        raise ValueError("%s: q is %s, d_out is %s" % (who, q.dtype, d_out.dtype))
+    if d_out.dim() != 3 or tuple(d_out.shape) != (n_pairs, Lq, E) or d_out.stride(2) != 1:
+        raise ValueError("%s: d_out must be (%d, %d, %d) with contiguous columns (got %s, strides %s)"
+                         % (who, n_pairs, Lq, E, tuple(d_out.shape), d_out.stride()))
+    if (sites is None) != (d_sites is None):
+        raise ValueError("%s: sites and d_sites are given both or neither" % who)
+    if sites is not None:
+        if sites.dim() != 3 or sites.shape[:2] != q.shape[:2] or sites.dtype != q.dtype or sites.stride(2) != 1:
+            raise ValueError("%s: sites must be (n_q, Lq, cols) of q's dtype with contiguous columns" % who)
+        if (d_sites.dim() != 3 or tuple(d_sites.shape) != (n_pairs, Lq, sites.shape[2]) or d_sites.dtype != q.dtype
+                or d_sites.stride(2) != 1):
+            raise ValueError("%s: d_sites must be (%d, %d, %d) of q's dtype with contiguous columns" % (who, n_pairs, Lq, sites.shape[2]))
+    if out is None:
+        out = (torch.empty((n_pairs, cols), dtype=torch.float32, device=q.device),
+               torch.empty((n_pairs, Lq), dtype=torch.float32, device=q.device))
+    else:
+        ok = isinstance(out, (tuple, list)) and len(out) == 2
+        for t, width in zip(out if ok else (), (cols, Lq)):
+            ok = ok and (t.dim() == 2 and t.dtype == torch.float32 and t.device == q.device and t.shape[0] == n_pairs
+                         and t.shape[1] >= width and t.stride(1) == 1 and t.stride(0) >= width)
+        if not ok:
+            raise ValueError("%s: out must be (key_attr float32 (%d, >= %d), site_attr float32 (%d, >= %d)) on q's device with "
+                             "contiguous columns and non-overlapping rows" % (who, n_pairs, cols, n_pairs, Lq))
+        out = tuple(out)
+    kattr, sattr = out
+    a.Q, a.K, a.dO, a.sites, a.d_sites = q.data_ptr(), store.data_ptr(), d_out.data_ptr(), _ptr(sites), _ptr(d_sites)
+    a.key_attr, a.site_attr = kattr.data_ptr(), sattr.data_ptr()
+    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
+    a.q_es, a.q_rs = q.stride(0), q.stride(1)
+    a.k_rs = store.stride(-2)
+    a.do_ps, a.do_rs = d_out.stride(0), d_out.stride(1)
+    if sites is not None:
+        a.left_es, a.left_rs = sites.stride(0), sites.stride(1)
+        a.dl_ps, a.dl_rs = d_sites.stride(0), d_sites.stride(1)
+        a.left_cols = sites.shape[2]
+    a.mass_ps, a.site_ps = kattr.stride(0), sattr.stride(0)
+    a.n_pairs, a.n_q, a.Lq, a.head_dim, a.dtype = n_pairs, n_q, Lq, E, _dt(q)
+    a.out_cols = cols
+    a.scale = float(scale)
+    return out
+
+
+def pgca_pairs_attr(q, kv, d_out, q_index, kv_index, *, scale, key_tail=None, cols=None, sites=None, d_sites=None, out=None):
+    """Hit attributions of (protein, drug) pairs over cached entity codes (dl_pgca_pairs_attr): gradient x code at the pair-stage
+    interface, from ONE launch that forms no dQ, dK or dV'.  d_out (n_pairs, Lq, 128) is the gradient of a target w.r.t. the
+    attention output of pair n (contiguous columns, any 16-byte-aligned row and pair strides: the right half of a concat's
+    gradient is fine).  Returns (key_attr (n_pairs, cols) fp32: per drug key, (<dK_c, K_c> + <dV'_c, V'_c>) for ONE copy of the
+    key, at the column of every copy as pgca_pairs_profile's key_mass lays them out, +0.0 behind the drug's full key count;
+    site_attr (n_pairs, Lq) fp32: per protein site, <dq_r, q_r>, plus <d_sites_r, sites_r> when sites (n_q, Lq, c) and d_sites
+    (n_pairs, Lq, c) are given — both or neither).  The leaves are the cached codes q, sites and [K | V'], not the raw inputs
+    in front of the encoders; the values are signed.  q, kv, key_tail, cols and the flags as in pgca_pairs_profile; out: the two
+    tensors to write into (rows may be wider)."""
+    _need_gpu(q, kv, d_out, q_index, kv_index, sites, d_sites, *(out if isinstance(out, (tuple, list)) else ()))
+    a = PgcaPairsAttrArgs()
+    t, w = (int(key_tail[0]), float(key_tail[1])) if key_tail is not None else (0, 1.0)
+    if cols is None and kv.dim() == 3:
+        cols = kv.shape[1] - t + t * int(w) if t else kv.shape[1]
+    out = _pgca_attr_common("pgca_pairs_attr", a, q, kv, "kv", ("n_kv", "Lk"), d_out, q_index, kv_index, scale, cols or 0, sites, d_sites, out)
+    a.k_es = kv.stride(0)
+    a.n_kv, a.Lk = kv.shape[:2]
+    if key_tail is not None:
+        a.key_tail_rows, a.key_tail_weight = t, w
+    check(_lib.lib().dl_pgca_pairs_attr(C.byref(a), _stream()), "dl_pgca_pairs_attr")
+    return out
+
+
+def pgca_pairs_ragged_attr(q, rows, row0, n_keys, tail_weight, d_out, q_index, kv_index, *, scale, key_tail_rows, cols, sites=None,
+                           d_sites=None, out=None):
+    """pgca_pairs_attr over a packed per-drug row store (dl_pgca_pairs_ragged_attr; screening.DrugLibrary): the key table is
+    pgca_pairs_ragged's, the columns those of the drug's full key set (n_keys[d] - key_tail_rows + key_tail_rows *
+    tail_weight[d] of `cols`).  Gradient x code at the pair-stage interface: the leaves are the cached codes, not the raw inputs.
+    A pair is skipped — neither output is written for it — and flagged in the device guard word (check_guard_flags) under
+    pgca_pairs_ragged_profile's conditions."""
+    _need_gpu(q, rows, row0, n_keys, tail_weight, d_out, q_index, kv_index, sites, d_sites, *(out if isinstance(out, (tuple, list)) else ()))
+    _check_key_table("pgca_pairs_ragged_attr", q, row0, n_keys, tail_weight)
+    if int(key_tail_rows) < 0:
+        raise ValueError("pgca_pairs_ragged_attr: key_tail_rows %d is negative" % int(key_tail_rows))
+    a = PgcaPairsRaggedAttrArgs()
+    out = _pgca_attr_common("pgca_pairs_ragged_attr", a, q, rows, "rows", ("R",), d_out, q_index, kv_index, scale, cols, sites, d_sites, out)
+    a.kv_row0, a.kv_keys, a.kv_tail_weight = row0.data_ptr(), n_keys.data_ptr(), tail_weight.data_ptr()
+    a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
+    a.key_tail_rows = int(key_tail_rows)
+    check(_lib.lib().dl_pgca_pairs_ragged_attr(C.byref(a), _stream()), "dl_pgca_pairs_ragged_attr")
     return out
 
 

@@ -37,6 +37,8 @@ from .model.basic_model import binary_cross_entropy, cross_entropy_logits
 
 # Trainer.hit_profiles: key_mass (P, k, cols) fp32, site_peak (P, k, n_site) fp32, site_key (P, k, n_site) int32, on the CPU
 HitProfiles = collections.namedtuple("HitProfiles", "key_mass site_peak site_key")
+# Trainer.hit_attributions: logit (P, k) fp32, key_attr {branch: (P, k, cols_b)} fp32, site_attr {branch: (P, k, n_site)} fp32, on the CPU
+HitAttributions = collections.namedtuple("HitAttributions", "logit key_attr site_attr")
 
 
 class CosineAnnealingWarmupRestarts:
@@ -1092,22 +1094,49 @@ class Trainer:
                                torch.zeros((0, k, 0), dtype=torch.int32))
         return HitProfiles(*(o.view(P, k, o.shape[1]) for o in outs))
 
+    def hit_attributions(self, protein_batches, lib, indices, pair_batch: int = 64) -> HitAttributions:
+        """Gradient x code attributions of screening hits: what moves the score, where hit_profiles says where the attention
+        looks.  For protein p and its j-th hit, drug indices[p, j]: logit[p, j] is the logit whose sigmoid screen_library
+        reports; key_attr[branch][p, j, c] the share of it that gradient x code assigns to drug key c (one copy's value, in
+        hit_profiles' key_mass columns: cols_b = the largest full key count among the hits in that branch, +0.0 behind a
+        drug's own) and site_attr[branch][p, j, r] the share of protein site r.  The leaves are the cached codes at the pair
+        stage, not the raw inputs; the values are signed.  Returns HitAttributions(logit (P, k) fp32, key_attr {branch:
+        (P, k, cols_b)} fp32, site_attr {branch: (P, k, n_site)} fp32) on the CPU.  The protein batches are streamed and the
+        arguments checked as in hit_profiles; every branch of a chunk of pair_batch pairs comes from ONE tail backward
+        (model.attribute_library)."""
+        names = sorted(lib.branches)
+
+        def fetch(pcode, pi, di, cols):
+            logit, per = self.model.attribute_library(pcode, lib, pi, di, cols=cols)
+            return (logit,) + tuple(t for b in names for t in per[b])
+        P, k, cols, outs = self._hit_stream("hit_attributions", protein_batches, lib, indices, names, pair_batch, fetch)
+        if outs is None:
+            z = lambda: {b: torch.zeros((0, k, 0), dtype=torch.float32) for b in names}
+            return HitAttributions(torch.zeros((0, k), dtype=torch.float32), z(), z())
+        shaped = [o.view(P, k, o.shape[1]) for o in outs[1:]]
+        return HitAttributions(outs[0].view(P, k), {b: shaped[2 * i] for i, b in enumerate(names)},
+                               {b: shaped[2 * i + 1] for i, b in enumerate(names)})
+
     def _hit_stream(self, who, protein_batches, lib, indices, branch, pair_batch, fetch):
-        """What hit_maps and hit_profiles share: the checks of their arguments, the streaming of the protein batches and the
-        chunking of the hits.  fetch(pcode, pi, di, cols) gives a chunk's results as a tuple of device tensors whose first
-        dimension is the pair; each is copied to the host behind the chunks before it.  Returns (P, k, cols, the tuple of
-        (P * k, ...) CPU tensors, or None where no protein came)."""
+        """What hit_maps, hit_profiles and hit_attributions share: the checks of their arguments, the streaming of the protein
+        batches and the chunking of the hits.  fetch(pcode, pi, di, cols) gives a chunk's results as a tuple of device tensors
+        whose first dimension is the pair; each is copied to the host behind the chunks before it.  branch: one branch (cols:
+        an int), or a list of branches (cols: {branch: int}).  Returns (P, k, cols, the tuple of (P * k, ...) CPU tensors, or
+        None where no protein came)."""
         if pair_batch < 1:
             raise ValueError("%s: pair_batch must be positive" % who)
-        if branch not in lib.branches:
-            raise ValueError("%s: unknown branch %r (the library has %s)" % (who, branch, sorted(lib.branches)))
+        per_branch = not isinstance(branch, str)                # hit_attributions: every branch at once, cols = {branch: columns}
+        for b in (branch if per_branch else (branch,)):
+            if b not in lib.branches:
+                raise ValueError("%s: unknown branch %r (the library has %s)" % (who, b, sorted(lib.branches)))
         idx = torch.as_tensor(indices, dtype=torch.int64).cpu()
         if idx.dim() != 2:
             raise ValueError("%s: indices must be (P, k), got %s" % (who, tuple(idx.shape),))
         P, k = idx.shape
         if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= lib.n):
             raise IndexError("%s: drug index out of range [0, %d)" % (who, lib.n))
-        cols = int(lib.full_keys(branch)[idx.reshape(-1)].max()) if idx.numel() else 0
+        full = lambda b: int(lib.full_keys(b)[idx.reshape(-1)].max()) if idx.numel() else 0
+        cols = {b: full(b) for b in branch} if per_branch else full(branch)
         self.model.eval()
         outs, p0 = None, 0
         for feat_p, llm_p in protein_batches:

@@ -569,6 +569,60 @@ typedef struct {
 } dl_pgca_pairs_ragged_profile_args;
 int dl_pgca_pairs_ragged_profile(const dl_pgca_pairs_ragged_profile_args* a, dl_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Pair-indexed PGCA hit attributions: gradient x code of a target at the pair stage, per drug key and
+ * per protein site, from the cached operands and the gradient of the pair's concat row, WITHOUT forming
+ * dQ, dK or dV' (csrc/pgca_pairs_attr.hip).  dl_pgca_pairs_attr takes dense codes, dl_pgca_pairs_ragged_attr
+ * the packed row store and its device table, exactly as the profile entry points do; both launch one
+ * kernel, and on a store of equal-length drugs they give the same bits.
+ *
+ * K points at [K | V'] rows: V'_c is columns head_dim .. 2 head_dim - 1 of the row K_c (k_rs >= 2 head_dim).
+ * For pair n < n_pairs with p = q_index[n], d = kv_index[n], w_c the multiplicity of stored key c (1 for
+ * c < lead_d, w_d on the last t rows), dO (n, r, :) the gradient w.r.t. the attention output of row r:
+ *   s[r,c]  = scale Q[p]_r . K_d,c          p[r,c] = exp(s[r,c]) / sum_c' w_c' exp(s[r,c'])
+ *   g[r,c]  = dO[n]_r . V'_d,c              D[r]   = sum_c w_c p[r,c] g[r,c]       ds[r,c] = p[r,c] (g[r,c] - D[r])
+ *   key_attr  (n, col) = sum_r (ds[r,c] s[r,c] + p[r,c] g[r,c])   one copy's value of stored key c, at every column
+ *                        of the key's copies (copy i of tail key j at lead_d + i * t + j, as key_mass); +0.0f for
+ *                        F_d <= col < out_cols.  It equals (dK_c . K_c + dV'_c . V'_c) / w_c.
+ *   site_attr (n, r)   = sum_c w_c ds[r,c] s[r,c]  (+ d_sites (n, r, :) . sites (p, r, :) over left_cols columns when
+ *                        sites / d_sites are given: both or neither)          r < Lq.  It equals dq_r . q_r (+ the left dot).
+ * The tail bias log w enters the normaliser only, never the factor s[r,c].  All sums are fp32.
+ * Addressing (element strides; every operand dtype `dtype` with contiguous columns; outputs fp32):
+ *   q      (e, r, :) = Q + e*q_es + r*q_rs               K_d as in the profile entry points
+ *   dO     (n, r, :) = dO + n*do_ps + r*do_rs            sites (e, r, :) = sites + e*left_es + r*left_rs
+ *   d_sites(n, r, :) = d_sites + n*dl_ps + r*dl_rs
+ *   key_attr (n, c)  = key_attr + n*mass_ps + c          site_attr (n, r) = site_attr + n*site_ps + r
+ * Nothing else is written.  One launch, no workspace, no atomics on data: two calls agree bitwise.
+ * A pair is skipped, with the flags and under the conditions of the profile entry points (more than 576 stored
+ * keys included).  One head, head_dim == 128; Lq arbitrary; Q / K / dO / sites / d_sites 16-byte aligned with strides
+ * multiples of 16 bytes, left_cols a multiple of 16 bytes; the outputs and index vectors 4-byte, kv_row0 8-byte
+ * aligned; mass_ps >= out_cols > 0, site_ps >= Lq; reserved == 0.  n_pairs == 0: DL_OK, nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* Q; const void* K; const void* dO; const void* sites; const void* d_sites; float* key_attr; float* site_attr;
+  const int32_t* q_index; const int32_t* kv_index; uint32_t* flags;
+  int64_t q_es, q_rs, k_es, k_rs, do_ps, do_rs, left_es, left_rs, dl_ps, dl_rs, mass_ps, site_ps;
+  int32_t n_pairs, n_q, n_kv, Lq, Lk, head_dim, dtype;
+  int32_t out_cols, left_cols;
+  float scale;
+  int32_t key_tail_rows; float key_tail_weight;
+  int32_t reserved;
+} dl_pgca_pairs_attr_args;
+int dl_pgca_pairs_attr(const dl_pgca_pairs_attr_args* a, dl_stream s);
+
+typedef struct {
+  const void* Q; const void* K; const void* dO; const void* sites; const void* d_sites; float* key_attr; float* site_attr;
+  const int32_t* q_index; const int32_t* kv_index;
+  const int64_t* kv_row0; const int32_t* kv_keys; const float* kv_tail_weight; uint32_t* flags;
+  int64_t q_es, q_rs, k_rs, do_ps, do_rs, left_es, left_rs, dl_ps, dl_rs, mass_ps, site_ps, kv_total_rows;
+  int32_t n_pairs, n_q, n_kv, Lq, head_dim, dtype;
+  int32_t out_cols, left_cols;
+  float scale;
+  int32_t key_tail_rows;
+  int32_t reserved;
+} dl_pgca_pairs_ragged_attr_args;
+int dl_pgca_pairs_ragged_attr(const dl_pgca_pairs_ragged_attr_args* a, dl_stream s);
+
 
 /* ------------------------------------------------------------------------------------------
  * MHLA token gate (MultiHeadLinearAttention.forward, model/PMMA/encoder.py:127-140):
