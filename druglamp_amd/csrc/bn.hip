@@ -150,7 +150,7 @@ __global__ void bn_apply_fwd_kernel(const T* __restrict__ y, T* __restrict__ z, 
     o = (v - mu) * rs * g + b;
     if constexpr (RELU) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
+      for (int e = 0; e < 4; ++e) o[e] = max_keep_nan(o[e], 0.f);
     }
   }
   store4<T>(z + r * C + c, o);
@@ -494,7 +494,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sums, float inv_n, 
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const float m = sums[c] * inv_n;
-  const float v = fmaxf(sums[C + c] * inv_n - m * m, 0.f);
+  const float v = max_keep_nan(sums[C + c] * inv_n - m * m, 0.f);   // (inf - inf and NaN sums stay NaN)
   mean[c] = m;
   var[c] = v;
   rstd[c] = rsqrtf(v + eps);
@@ -550,7 +550,7 @@ __global__ __launch_bounds__(1024) void bn_reduce_finalize_kernel(const float* _
     if (sums) sums[c] = red[0][cl];
     if (cl < 8) {
       const float m = red[0][cl] * inv_n;
-      const float v = fmaxf(red[0][cl + 8] * inv_n - m * m, 0.f);
+      const float v = max_keep_nan(red[0][cl + 8] * inv_n - m * m, 0.f);
       mean[ch] = m;
       var[ch] = v;
       rstd[ch] = rsqrtf(v + eps);

@@ -246,6 +246,9 @@ template <int FAM, typename T> __device__ __forceinline__ void store4_fam(T* p, 
 
 
 // ---- math ---------------------------------------------------------------------------------
+// max(x, lo) that KEEPS a NaN of x (torch.relu / torch.clamp(min=lo) semantics; fmaxf returns the operand that is not NaN and
+// would turn a poisoned pre-activation into a clean 0).  llvm.maximum; what it compiles to: DESIGN.md, "Non-finite values".
+__device__ __forceinline__ float max_keep_nan(float x, float lo) { return __builtin_elementwise_maximum(x, lo); }
 __device__ __forceinline__ float gelu_erf(float x) {
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }

@@ -402,8 +402,8 @@ __global__ __launch_bounds__(256) void norm_adj_kernel(const float* __restrict__
   __syncthreads();
   for (int r = tid; r < 2 * n; r += 256) {
     float sum = 0.f;
-    if (r < n) { for (int i = 0; i < n; ++i) sum += a[r * P + i]; dout[r] = rsqrtf(fmaxf(sum, 1.f)); }
-    else { const int c = r - n; for (int j = 0; j < n; ++j) sum += a[j * P + c]; din[c] = rsqrtf(fmaxf(sum, 1.f)); }
+    if (r < n) { for (int i = 0; i < n; ++i) sum += a[r * P + i]; dout[r] = rsqrtf(max_keep_nan(sum, 1.f)); }
+    else { const int c = r - n; for (int j = 0; j < n; ++j) sum += a[j * P + c]; din[c] = rsqrtf(max_keep_nan(sum, 1.f)); }
   }
   __syncthreads();
   TO* dst = ahat + (int64_t)b * n * n;
@@ -424,8 +424,8 @@ __global__ __launch_bounds__(256) void norm_adj_any_kernel(const float* __restri
   const float* a = adj + (int64_t)b * n * n;
   for (int r = tid; r < 2 * n; r += 256) {
     float sum = 0.f;
-    if (r < n) { for (int i = 0; i < n; ++i) sum += a[(int64_t)r * n + i]; dout[r] = rsqrtf(fmaxf(sum, 1.f)); }
-    else { const int c = r - n; for (int j = 0; j < n; ++j) sum += a[(int64_t)j * n + c]; din[c] = rsqrtf(fmaxf(sum, 1.f)); }
+    if (r < n) { for (int i = 0; i < n; ++i) sum += a[(int64_t)r * n + i]; dout[r] = rsqrtf(max_keep_nan(sum, 1.f)); }
+    else { const int c = r - n; for (int j = 0; j < n; ++j) sum += a[(int64_t)j * n + c]; din[c] = rsqrtf(max_keep_nan(sum, 1.f)); }
   }
   __syncthreads();
   TO* dst = ahat + (int64_t)b * n * n;

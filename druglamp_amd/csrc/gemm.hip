@@ -369,7 +369,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmP p0) {
         a0 = gelu4<T>(a0); a1 = gelu4<T>(a1);
       } else if constexpr (EPI == 5) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { a0[r] = fmaxf(a0[r], 0.f); a1[r] = fmaxf(a1[r], 0.f); }
+        for (int r = 0; r < 4; ++r) { a0[r] = max_keep_nan(a0[r], 0.f); a1[r] = max_keep_nan(a1[r], 0.f); }
       } else if constexpr (EPI == 4) {
         const T* src = reinterpret_cast<const T*>(p.dact_pre) + (int64_t)m * p.lddp + n;
         const f32x4 q0 = load4<T>(src), q1 = load4<T>(src + 4);
@@ -429,7 +429,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmP p0) {
         for (int r = 0; r < 8; ++r) v[r] = gelu_erf(v[r]);
       } else if (p.act == 2) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = fmaxf(v[r], 0.0f);
+        for (int r = 0; r < 8; ++r) v[r] = max_keep_nan(v[r], 0.f);
       }
       if (p.dact_pre) {
         const T* src = reinterpret_cast<const T*>(p.dact_pre) + (int64_t)m * p.lddp + n;

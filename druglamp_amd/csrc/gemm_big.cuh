@@ -39,7 +39,7 @@ __device__ __forceinline__ void big_epilogue8(const GemmP& p, uint64_t seed_eff,
     a0 = gelu4<T>(a0); a1 = gelu4<T>(a1);
   } else if constexpr (EPI == 5) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { a0[r] = fmaxf(a0[r], 0.f); a1[r] = fmaxf(a1[r], 0.f); }
+    for (int r = 0; r < 4; ++r) { a0[r] = max_keep_nan(a0[r], 0.f); a1[r] = max_keep_nan(a1[r], 0.f); }
   } else if constexpr (EPI == 4) {
     a0 *= gelu_grad4<T>(f32x4{bf16lo(ext[0]), bf16hi(ext[0]), bf16lo(ext[1]), bf16hi(ext[1])});
     a1 *= gelu_grad4<T>(f32x4{bf16lo(ext[2]), bf16hi(ext[2]), bf16lo(ext[3]), bf16hi(ext[3])});

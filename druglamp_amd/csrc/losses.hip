@@ -28,7 +28,7 @@ __global__ void cos_rowloss_fwd_kernel(const float* __restrict__ x, const float*
   }
   dot = wave_sum(dot); nx = wave_sum(nx); ny = wave_sum(ny);
   if (lane == 0) {
-    const float dx = fmaxf(sqrtf(nx), NORM_EPS), dy = fmaxf(sqrtf(ny), NORM_EPS);
+    const float dx = max_keep_nan(sqrtf(nx), NORM_EPS), dy = max_keep_nan(sqrtf(ny), NORM_EPS);
     row_loss[row] = 2.0f - 2.0f * dot / (dx * dy);
   }
 }
@@ -62,7 +62,7 @@ __global__ void cos_rowloss_bwd_kernel(const float* __restrict__ x, const float*
   }
   dot = wave_sum(dot); nx = wave_sum(nx); ny = wave_sum(ny);
   const float nxs = sqrtf(nx);
-  const float dx = fmaxf(nxs, NORM_EPS), dy = fmaxf(sqrtf(ny), NORM_EPS);
+  const float dx = max_keep_nan(nxs, NORM_EPS), dy = max_keep_nan(sqrtf(ny), NORM_EPS);   // (fmaxf would turn a NaN norm into eps: a1 finite, a2 = 0, a clean-looking gradient)
   // cos = dot / (dx*dy); d cos / d x = y/(dx*dy) - dot * x / (dx^3 * dy)   (when ||x|| > eps)
   const float a1 = -2.0f * gscale / (dx * dy);
   const float a2 = (nxs > NORM_EPS) ? 2.0f * gscale * dot / (dx * dx * dx * dy) : 0.f;
@@ -223,7 +223,7 @@ __global__ void row_norm_kernel(const float* __restrict__ X, int n, int dim, flo
   float s = 0.f;
   for (int c = lane; c < dim; c += 64) { const float a = X[(int64_t)i * dim + c]; s += a * a; }
   s = wave_sum(s);
-  if (lane == 0) out[i] = fmaxf(sqrtf(s), COS_EPS);
+  if (lane == 0) out[i] = max_keep_nan(sqrtf(s), COS_EPS);
 }
 
 // block = 4 waves, wave handles one anchor i and loops over j
@@ -288,6 +288,8 @@ __global__ void triplet_reduce_kernel(const float* __restrict__ dist, const floa
       if (hv > 0.f) {
         s += hv;
         if (gcoef) { atomicAdd(&gcoef[(int64_t)i * n_d + pj], 1.0f); atomicAdd(&gcoef[(int64_t)i * n_d + nj], -1.0f); }
+      } else if (hv != hv) {
+        s += hv;                                     // relu(NaN) is NaN: the hinge poisons the loss; its gradient is a closed ReLU's (no coefficient)
       }
     }
   } else if (nn_ > 0) {
@@ -297,6 +299,7 @@ __global__ void triplet_reduce_kernel(const float* __restrict__ dist, const floa
       const int nj = neg[t];
       const float hv = dself - drow[nj] + margin;
       if (hv > 0.f) { s += hv; if (gcoef) atomicAdd(&gcoef[(int64_t)i * n_d + nj], -1.0f); }
+      else if (hv != hv) s += hv;
     }
   }
   s = wave_sum(s);
@@ -333,8 +336,8 @@ __global__ void triplet_bwd_p_kernel(const float* __restrict__ P, const float* _
     const float pc = P[(int64_t)i * dim + c];
     for (int j = 0; j < n_d; ++j) {
       const float gc = gcoef[(int64_t)i * n_d + j];
-      if (gc == 0.f) continue;
       const float cs = cosm[(int64_t)i * n_d + j];
+      if (gc == 0.f && cs == cs) continue;           // (a NaN cosine stays in: 0 x NaN poisons the gradient, as autograd's sigmoid backward does)
       const float sg = 1.0f / (1.0f + __expf(-cs));
       const float G = -sg * (1.0f - sg) * gc * gs;
       acc += G * (Dm[(int64_t)j * dim + c] / (np * dn[j]) - cs * pc / (np * np));
@@ -355,8 +358,8 @@ __global__ void triplet_bwd_d_kernel(const float* __restrict__ P, const float* _
     const float dc = Dm[(int64_t)j * dim + c];
     for (int i = 0; i < n_p; ++i) {
       const float gc = gcoef[(int64_t)i * n_d + j];
-      if (gc == 0.f) continue;
       const float cs = cosm[(int64_t)i * n_d + j];
+      if (gc == 0.f && cs == cs) continue;           // (a NaN cosine stays in: 0 x NaN poisons the gradient, as autograd's sigmoid backward does)
       const float sg = 1.0f / (1.0f + __expf(-cs));
       const float G = -sg * (1.0f - sg) * gc * gs;
       acc += G * (P[(int64_t)i * dim + c] / (pn[i] * nd) - cs * dc / (nd * nd));

@@ -195,7 +195,9 @@ __global__ __launch_bounds__(PROF_THREADS) void pgca_pairs_profile_kernel(const 
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) {
               const float pv = fast_exp2(s[qt][kt][r] * c - lse2[qt]);
-              if (key < Lk && pv > best_p[qt]) { best_p[qt] = pv; best_k[qt] = key; }   // keys ascend per lane: > keeps the smallest
+              // keys ascend per lane: > keeps the smallest.  A NaN probability wins and then stays (nothing compares above it): the
+              // maximum of a row that holds a NaN is NaN, as torch.max gives, where the bare compare left the initial -1 in place
+              if (key < Lk && (pv > best_p[qt] || pv != pv)) { best_p[qt] = pv; best_k[qt] = key; }
               v += valid[qt] ? pv : 0.f;
             }
             cs[r] = row16_sum(v);                       // over the 16 queries il of the row (every lane gets the sum)
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(PROF_THREADS) void pgca_pairs_profile_kernel(const 
       for (int off = 16; off <= 32; off <<= 1) {
         const float op = __shfl_xor(bp, off, 64);
         const int ok = __shfl_xor(bk, off, 64);
-        if (op > bp || (op == bp && ok < bk)) { bp = op; bk = ok; }
+        if (op > bp || op != op || (op == bp && ok < bk)) { bp = op; bk = ok; }
       }
       const int q = qw0 + qt * 16 + il;
       if (g == 0 && valid[qt]) { peak[q] = bp; skey[q] = bk; }

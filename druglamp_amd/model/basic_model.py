@@ -32,7 +32,16 @@ CONFIGS = {"LAMP": get_model_defaults}
 
 def binary_cross_entropy(pred_output, labels):
     n = torch.sigmoid(pred_output.float()).squeeze(1)
-    return n, F.binary_cross_entropy(n, labels.float())
+    # A NaN score must come out as a NaN loss (non-finite values).  torch's device kernel of binary_cross_entropy
+    # asserts 0 <= n <= 1, and on ROCm a failed device assert is abort(): a NaN score killed the process in the middle of the
+    # backward, without a message.  The kernel therefore sees 0.5 in place of a NaN, and the loss is multiplied by NaN behind
+    # it, so that the loss AND every gradient of the step are NaN, as torch's own CPU arithmetic would give; for finite scores
+    # the factor is 1.0 and the loss and its gradient are bit for bit what F.binary_cross_entropy(n, labels) gives.  No host
+    # synchronisation: the step stays capturable as a graph.  Cost: five more small launches per step (isnan, masked_fill,
+    # any, where, mul) and two in the backward.
+    bad = torch.isnan(n)
+    loss = F.binary_cross_entropy(n.masked_fill(bad, 0.5), labels.float())
+    return n, loss * torch.where(bad.any(), float("nan"), 1.0)
 
 
 def cross_entropy_logits(linear_output, label, weights=None):

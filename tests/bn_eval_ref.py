@@ -39,11 +39,11 @@ def bn_eval_bwd(dz, y, w, mean, rstd, gamma, beta=None, relu_in=False, relu_out=
         bt = _d(beta)
         p = xh * gm + bt
         pre[keep], pre_mag[keep] = p, (xh * gm).abs() + bt.abs()
-        g = d * (p > 0)
+        g = torch.where(p > 0, d, torch.zeros_like(d))        # a select: a closed element's dz is not read
     s0, s1 = g.sum(0), (g * xh).sum(0)
     v = g * gm * rs
     if relu_in:
-        v = v * (yk > 0)
+        v = torch.where(yk > 0, v, torch.zeros_like(v))
     dx = torch.zeros((R, C), dtype=F64, device=y.device)
     dx[keep] = v
     mags = {"dx": dx.abs(), "s0": g.abs().sum(0), "s1": (g * xh).abs().sum(0), "pre": pre, "pre_mag": pre_mag, "xhat_abs": xhat_abs}

@@ -156,11 +156,11 @@ def ce_rows_bwd(logits, labels, C, ignore, lse, count, gout, Cp):
     p = torch.exp(x - lse.to(F64).unsqueeze(1))
     hot = torch.zeros_like(x)
     hot[torch.arange(N, device=x.device), labels.clamp(0, C - 1)] = 1.0
-    on = valid.to(F64).unsqueeze(1)
+    on = valid.unsqueeze(1)
     d = torch.zeros(N, Cp, dtype=F64, device=x.device)
     mag, xl = torch.zeros_like(d), torch.zeros_like(d)
-    d[:, :C] = on * g * (p - hot)
-    mag[:, :C] = on * abs(g) * (p + hot)
+    d[:, :C] = torch.where(on, g * (p - hot), torch.zeros_like(p))            # a select: an uncounted row's logits are not read
+    mag[:, :C] = torch.where(on, abs(g) * (p + hot), torch.zeros_like(p))
     xl[:, :C] = (x - lse.to(F64).unsqueeze(1)).abs()
     return {"dlogits": d, "mag": mag, "xl": xl}
 

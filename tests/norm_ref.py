@@ -124,7 +124,7 @@ def bn_bwd_sums(dz, y, w, mean, rstd, gamma=None, beta=None):
     keep = w >= 0
     d, yh = _d(dz[keep]), _yhat(y[keep], mean, rstd)
     if gamma is not None:
-        d = d * _open(y[keep], mean, rstd, gamma, beta)
+        d = torch.where(_open(y[keep], mean, rstd, gamma, beta), d, torch.zeros_like(d))     # a select: a closed element's dz is not read
     return d.sum(0), (d * yh).sum(0), {"s0": d.abs().sum(0), "s1": (d * yh).abs().sum(0)}
 
 
@@ -138,11 +138,11 @@ def bn_bwd_apply(dz, y, w, mean, rstd, gamma, s0, s1, inv_n, relu_mask=False, be
     d, yk, wk = _d(dz[keep]), _d(y[keep]), _d(w[keep])[:, None]
     yh = (yk - _d(mean)) * rs
     if beta is not None:
-        d = d * _open(y[keep], mean, rstd, gamma, beta)
+        d = torch.where(_open(y[keep], mean, rstd, gamma, beta), d, torch.zeros_like(d))
     v = g * rs * (d - wk * (s0 * inv_n + yh * (s1 * inv_n)))
     m = (g * rs).abs() * (d.abs() + wk * (s0.abs() * inv_n + yh.abs() * (s1.abs() * inv_n)))
     if relu_mask:
-        v, m = v * (yk > 0), m * (yk > 0)
+        v, m = torch.where(yk > 0, v, torch.zeros_like(v)), torch.where(yk > 0, m, torch.zeros_like(m))
     dy = torch.zeros((R, C), dtype=F64, device=y.device)
     mag = torch.zeros_like(dy)
     dy[keep], mag[keep] = v, m

@@ -31,7 +31,8 @@ operands, so every error is the kernel's rounding.  S = sum_k |X||W| per output 
   accumulation   e = (K + splits + 2) 2 U_F S.  bf16 products are exact in fp32, fp32 products round once; every add is counted
                  at one whole ulp because MFMA-internal adds need not round to nearest; `splits` adds for the slab reduction.
   bias           + U_F |pre|.  pre_out: e + U_st |pre| (U_st = U_B for bf16 storage, U_F for fp32).
-  activation     ReLU: Lipschitz 1, max() is exact.  GELU: Lipschitz 1.13, so e <- 1.13 e, plus 4 U_F |gelu| for the erff forms
+  activation     ReLU: Lipschitz 1, the maximum is exact for numbers, and it KEEPS a NaN or +inf of the pre-activation (max_keep_nan,
+                 common.cuh; -inf gives 0): tests/test_nonfinite_paths_gpu.py.  GELU: Lipschitz 1.13, so e <- 1.13 e, plus 4 U_F |gelu| for the erff forms
                  (the cancellation in 1 + erf for negative arguments costs at most U_F |pre| <= U_F (S + |bias|), which the
                  accumulation term holds several times over), plus the documented absolute 7.1e-5 of gelu_fast2 in the bf16
                  specialised epilogues (|pre| <= 12, asserted on the data).

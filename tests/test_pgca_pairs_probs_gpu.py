@@ -79,8 +79,7 @@ def _drug_map(Q, K, t, w, expand, scale):
     return pm, MARGIN * pm * rel + FLOOR, lk_full, float(lam.max())
 
 
-@functools.lru_cache(maxsize=None)
-def _setup(name, dt, expand, dev=DEV):
+def build(name, dt, expand, dev=DEV):
     """Inputs of a case and its fp64 reference (computed once per (protein, drug), shared by the tests that use the case, never
     modified).
 
@@ -128,6 +127,12 @@ def _setup(name, dt, expand, dev=DEV):
         lam = max(lam, lm)
     return dict(c=c, dt=dt, expand=expand, scale=scale, q=q, rows=store[:R], n_kv=n_kv, row0=t_row0, keys=t_keys, w=t_w, pi=pi, di=di,
                 n=n, want=want, bound=bound, ncols=ncols, full=full, lam=lam)
+
+
+@functools.lru_cache(maxsize=None)
+def _setup(name, dt, expand, dev=DEV):
+    """build(), computed once per case and shared by the tests of this file, which never modify it."""
+    return build(name, dt, expand, dev)
 
 
 def _out_store(n, Lq, cols, pitch):

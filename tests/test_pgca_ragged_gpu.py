@@ -62,8 +62,7 @@ def _nan_view(n_ent, L, cols, dt, fill, dev):
     return v
 
 
-@functools.lru_cache(maxsize=None)
-def _setup(name, dt, dev=DEV):
+def build(name, dt, dev=DEV):
     """Inputs of a case and its fp64 reference (computed once, shared by the tests that use the case, never modified).
 
     Row store: the drugs' segments back to back with a NaN segment of GAP rows in front of the middle drug and one behind the
@@ -113,6 +112,12 @@ def _setup(name, dt, dev=DEV):
     assert set(c.di) == set(range(n_kv)), "every drug of the case is used"
     return dict(c=c, dt=dt, scale=scale, q=q, rows=store[:R], n_kv=n_kv, row0=t_row0, keys=t_keys, w=t_w, left=left, bias=bias,
                 pi=pi, di=di, n=n, O=O, bound=TAU_O[dt] * mag + 1e-300, lam=lam)
+
+
+@functools.lru_cache(maxsize=None)
+def _setup(name, dt, dev=DEV):
+    """build(), computed once per case and shared by the tests of this file, which never modify it."""
+    return build(name, dt, dev)
 
 
 def _out_store(s):
