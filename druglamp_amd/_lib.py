@@ -306,6 +306,10 @@ SIGNATURES = {
     "dl_triplet_sigcos_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp]),
     "dl_adamw_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_f32, c_vp,
                               c_i32, c_vp]),
+    "dl_grad_sqnorm": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    "dl_grad_guard_finalize": (c_i32, [c_vp, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp]),
+    "dl_adamw_step_guarded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_f32, c_vp,
+                                      c_i32, c_vp, c_vp]),
     "dl_bn_stats_rw": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp, c_sz, c_vp]),
     "dl_bn_apply_fwd_rw": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_vp]),
     "dl_bn_bwd_reduce_rw": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp, c_sz, c_vp]),

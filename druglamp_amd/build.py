@@ -77,7 +77,10 @@ def _stale(out, deps):
 # bn_eval.hip gets the flag: its 16-byte form is the unpack-then-fp32 pattern above, it is HBM-bound (the packed forms buy
 # nothing) and tests/test_contention_gpu.py does not cover it.  tests/test_bn_eval_bwd_gpu.py passes with the flag and, in an
 # A/B build (DL_BUILD_NOSLP_FILES=norm.hip,elementwise.hip), without it: the choice is caution, not a failing test.
-FILE_FLAGS = {"norm.hip": ["-fno-slp-vectorize"], "elementwise.hip": ["-fno-slp-vectorize"], "bn_eval.hip": ["-fno-slp-vectorize"]}
+# grad_guard.hip gets the flag: its guarded AdamW kernel is elementwise.hip's arithmetic (csrc/adamw.cuh), and the two must give
+# the same bits.
+FILE_FLAGS = {"norm.hip": ["-fno-slp-vectorize"], "elementwise.hip": ["-fno-slp-vectorize"], "bn_eval.hip": ["-fno-slp-vectorize"],
+              "grad_guard.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src, force, objdir=OBJDIR, extra=()):

@@ -2,6 +2,7 @@
 // dropout re-application, casts, positional-table gradient, fused AdamW.
 #include <math.h>
 #include "common.cuh"
+#include "adamw.cuh"
 
 namespace {
 
@@ -636,35 +637,7 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                              float bc1, float bc2_sqrt, float gscale, TL* __restrict__ lowp) {
   const int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i4 >= n) return;
-  const int cnt = (int)min((int64_t)4, n - i4);
-  float pp[4], gg[4], mm[4], vv[4];
-  if (cnt == 4) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p + i4), b = *reinterpret_cast<const f32x4*>(g + i4);
-    const f32x4 c = *reinterpret_cast<const f32x4*>(m + i4), d = *reinterpret_cast<const f32x4*>(v + i4);
-    for (int j = 0; j < 4; ++j) { pp[j] = a[j]; gg[j] = b[j]; mm[j] = c[j]; vv[j] = d[j]; }
-  } else {
-    for (int j = 0; j < cnt; ++j) { pp[j] = p[i4 + j]; gg[j] = g[i4 + j]; mm[j] = m[i4 + j]; vv[j] = v[i4 + j]; }
-  }
-  for (int j = 0; j < cnt; ++j) {
-    const float grad = gg[j] * gscale;
-    float x = pp[j] * (1.0f - lr * wd);                    // decoupled weight decay
-    mm[j] = b1 * mm[j] + (1.0f - b1) * grad;               // torch: lerp / mul-add
-    vv[j] = b2 * vv[j] + (1.0f - b2) * grad * grad;
-    const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
-    x -= (lr / bc1) * (mm[j] / denom);
-    pp[j] = x;
-  }
-  if (cnt == 4) {
-    *reinterpret_cast<f32x4*>(p + i4) = f32x4{pp[0], pp[1], pp[2], pp[3]};
-    *reinterpret_cast<f32x4*>(m + i4) = f32x4{mm[0], mm[1], mm[2], mm[3]};
-    *reinterpret_cast<f32x4*>(v + i4) = f32x4{vv[0], vv[1], vv[2], vv[3]};
-    if (lowp) store4<TL>(lowp + i4, f32x4{pp[0], pp[1], pp[2], pp[3]});
-  } else {
-    for (int j = 0; j < cnt; ++j) {
-      p[i4 + j] = pp[j]; m[i4 + j] = mm[j]; v[i4 + j] = vv[j];
-      if (lowp) lowp[i4 + j] = from_f32<TL>(pp[j]);
-    }
-  }
+  adamw_thread<TL>(p, g, m, v, n, i4, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, lowp);   // (adamw.cuh: shared with dl_adamw_step_guarded)
 }
 
 inline uint32_t nblk(int64_t n, int t = 256) { return (uint32_t)((n + t - 1) / t); }
@@ -1185,8 +1158,8 @@ extern "C" int dl_adamw_step(float* param, const float* grad, float* exp_avg, fl
                              float grad_scale, void* param_lowp, int32_t lowp_dtype, dl_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   DL_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, DL_ERR_ARG, "dl_adamw_step: bad args");
-  const float bc1 = 1.0f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+  float bc1, bc2s;
+  adamw_bias_corrections(beta1, beta2, step, &bc1, &bc2s);
   const uint32_t blocks = nblk((n + 3) / 4);
   if (param_lowp && lowp_dtype == DL_BF16)
     hipLaunchKernelGGL((adamw_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq, n, lr,

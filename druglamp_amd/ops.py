@@ -889,6 +889,58 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, *, lr, beta1=0.9, beta2=0.999, 
                                    _stream()), "dl_adamw_step")
 
 
+# ---- gradient guard (csrc/grad_guard.hip): global-norm clipping and the non-finite step skip, decided on the device ----
+def grad_sqnorm_workspace_bytes(n: int) -> int:
+    """include/druglamp_hip.h: 8 * min(2048, ceil(n / 4096))."""
+    return 8 * min(2048, (int(n) + 4095) // 4096)
+
+
+def grad_sqnorm(g, acc, workspace, accumulate: bool = False):
+    """acc[0] (+)= sum of squares of the fp32 run g, in fp64, fixed order (two calls agree bitwise)."""
+    check(_lib.lib().dl_grad_sqnorm(g.data_ptr(), g.numel(), acc.data_ptr(), int(bool(accumulate)), workspace.data_ptr(),
+                                    workspace.numel() * workspace.element_size(), _stream()), "dl_grad_sqnorm")
+
+
+def grad_guard_finalize(acc, guard, counters, *, pre_scale: float = 1.0, max_norm: float = 0.0, skip_nonfinite: bool = False):
+    """acc -> guard = {clip coefficient, norm, skip flag, 0}; counters = {skipped, clipped} are added to."""
+    check(_lib.lib().dl_grad_guard_finalize(acc.data_ptr(), float(pre_scale), float(max_norm), int(bool(skip_nonfinite)),
+                                            guard.data_ptr(), counters.data_ptr(), _stream()), "dl_grad_guard_finalize")
+
+
+def adamw_step_guarded(param, grad, exp_avg, exp_avg_sq, guard, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, step,
+                       grad_scale=1.0, lowp=None):
+    """adamw_step with the gradient scaled by grad_scale * guard[0]; writes nothing when guard[2] != 0."""
+    n = param.numel()
+    check(_lib.lib().dl_adamw_step_guarded(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
+                                           float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+                                           float(grad_scale), _ptr(lowp), _DT[lowp.dtype] if lowp is not None else 0,
+                                           guard.data_ptr(), _stream()), "dl_adamw_step_guarded")
+
+
+class GradGuard:
+    """The device state of one trainer's gradient guard: the fp64 sum, the partials workspace (sized once for `numel`
+    elements: it serves any run of at most that many), guard = {coefficient, norm, skip flag, 0} and the cumulative
+    counters {skipped, clipped}.  max_norm <= 0: no clipping (the coefficient is exactly 1)."""
+
+    def __init__(self, numel: int, device, max_norm: float = 0.0, skip_nonfinite: bool = False):
+        self.max_norm, self.skip_nonfinite = float(max_norm), bool(skip_nonfinite)
+        self.acc = torch.zeros(1, dtype=torch.float64, device=device)
+        self.workspace = torch.empty(grad_sqnorm_workspace_bytes(numel) // 8, dtype=torch.float64, device=device)
+        self.guard = torch.zeros(4, dtype=torch.float32, device=device)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=device)
+
+    def decide(self, runs, pre_scale: float = 1.0):
+        """One decision from the gradient runs (flat fp32 tensors, 16-byte aligned): a sum-of-squares pass per run, then
+        the finalize launch.  No host synchronisation."""
+        if not runs:
+            self.acc.zero_()            # (no gradient at all: norm 0, nothing clipped, nothing skipped)
+        for k, g in enumerate(runs):
+            grad_sqnorm(g, self.acc, self.workspace, accumulate=k > 0)
+        grad_guard_finalize(self.acc, self.guard, self.counters, pre_scale=pre_scale, max_norm=self.max_norm,
+                            skip_nonfinite=self.skip_nonfinite)
+        return self.guard
+
+
 def cos_rowloss_fwd(x, y):
     n, D = x.shape
     row = torch.empty(n, dtype=torch.float32, device=x.device)

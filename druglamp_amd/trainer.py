@@ -19,7 +19,9 @@ What is new (MI355X-native):
     (which only reduces the cls backward that ran under the wrapper), the gradients the optimisers
     consume are reduced whichever loss produced them, so replicas never drift;
   * a backward pass whose gradients the next zero_grad wipes before any optimiser steps (cls on SSL / CM
-    steps, ssl on CM steps) is not run: the parameters after the step are the same, the step is shorter.
+    steps, ssl on CM steps) is not run: the parameters after the step are the same, the step is shorter;
+  * optional gradient guard (Trainer(max_grad_norm=..., skip_nonfinite=...)): global-norm clipping and the skip of a step with
+    a non-finite gradient, decided on the device from one fp64 pass over the flat gradient — no host round trip.
 """
 from __future__ import annotations
 
@@ -224,11 +226,18 @@ class FusedAdamW:
         self.exp_avg_sq = torch.zeros_like(flat.arena)
         self.steps = [0] * len(flat.params)
 
-    def step(self, idx: List[int], grad_scale: float = 1.0):
+    def step(self, idx: List[int], grad_scale: float = 1.0, guard: Optional[torch.Tensor] = None):
+        """guard (ops.GradGuard.guard, a device tensor): the guarded kernel scales the gradient by grad_scale * guard[0] and
+        writes nothing when guard[2] != 0.  The per-parameter step counts advance either way: the host does not know the
+        device's decision."""
         for s, e, first in self.flat.runs(idx, lambda i: self.steps[i]):
-            ops.adamw_step(self.flat.arena[s:e], self.flat.grads[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e],
-                           lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
-                           step=self.steps[first] + 1, grad_scale=grad_scale)
+            kw = dict(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
+                      step=self.steps[first] + 1, grad_scale=grad_scale)
+            if guard is None:
+                ops.adamw_step(self.flat.arena[s:e], self.flat.grads[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e], **kw)
+            else:
+                ops.adamw_step_guarded(self.flat.arena[s:e], self.flat.grads[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e],
+                                       guard, **kw)
         for i in idx:
             self.steps[i] += 1
 
@@ -451,10 +460,32 @@ class Trainer:
     grad_bf16 = False
     graph_allreduce = False
 
-    def __init__(self, model, cfg, device=None, compute_dtype=torch.float32, graph_steps: bool = False, freeze_bn: bool = False):
+    def __init__(self, model, cfg, device=None, compute_dtype=torch.float32, graph_steps: bool = False, freeze_bn: bool = False,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         """freeze_bn=True: fine-tuning with frozen BatchNorm (model.freeze_batchnorm()): every BatchNorm1d normalises with its
         running statistics, which the steps leave bitwise unchanged; its weight / bias train.  cls steps only (eager or
-        replayed): with the SSL or the CM head switched on (RS.SSL / RS.CM) construction raises."""
+        replayed): with the SSL or the CM head switched on (RS.SSL / RS.CM) construction raises.
+
+        max_grad_norm / skip_nonfinite: the gradient guard (off unless one of them is set; off = the launches of a step are
+        exactly those without it and no state is allocated).  On, every step — eager or replayed — measures the global L2 norm
+        of the AVERAGED gradient (the all-reduced flat buffer times 1 / world: the same bits on every rank, so replicas take
+        the same decision without another collective) with one fp64 pass over the gradient runs, decides ONCE on the
+        device, and all optimisers of the step (opt, opt_ssl, opt_cm read the same gradient) apply that decision:
+          * max_grad_norm (positive, finite): the gradient is scaled by min(1, max_grad_norm / (norm + 1e-6)), the formula
+            of torch.nn.utils.clip_grad_norm_;
+          * skip_nonfinite=True: a step whose gradient holds a NaN or an infinity is skipped — parameters, exp_avg and
+            exp_avg_sq keep their bits.  The host never learns of the skip (the step does not synchronise), so the
+            per-parameter step counts advance all the same and the bias correction of later steps counts the skipped
+            ones — unlike torch.cuda.amp.GradScaler, which does not count a skipped step; the price of a step that never
+            waits for the device.  BatchNorm running statistics are updated by the forward pass and are outside the
+            guard's reach: a forward that produced non-finite activations has already written them.
+        The step's result gains "grad_norm" (a device scalar); grad_guard_stats() reads the counters."""
+        if max_grad_norm is not None:
+            mg = float(max_grad_norm)
+            if not (mg > 0.0 and math.isfinite(mg)):
+                raise ValueError("Trainer(max_grad_norm=%r): must be None or a positive finite number" % (max_grad_norm,))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
         self.model = model
         self.cfg = cfg
         if freeze_bn:
@@ -486,7 +517,12 @@ class Trainer:
         self.opt = FusedAdamW(self.flat, cfg["SOLVER"]["LR"])
         self.opt_ssl = FusedAdamW(self.flat, cfg["SOLVER"]["SSL_LR"]) if self.use_ssl else None
         self.opt_cm = FusedAdamW(self.flat, cfg["SOLVER"]["CM_LR"]) if self.use_cm else None
-        self.schd = CosineAnnealingWarmupRestarts(self.epochs, cfg["SOLVER"]["LR"], 1e-8, warm)
+        self.grad_guard = None
+        self._guard_runs = None
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            self.grad_guard = ops.GradGuard(self.flat.numel, self.flat.grads.device, max_norm=self.max_grad_norm or 0.0,
+                                            skip_nonfinite=self.skip_nonfinite)
+        self.schd =CosineAnnealingWarmupRestarts(self.epochs, cfg["SOLVER"]["LR"], 1e-8, warm)
         self.schd_ssl = CosineAnnealingWarmupRestarts(self.epochs, cfg["SOLVER"]["SSL_LR"], 1e-8, warm) if self.use_ssl else None
         self.schd_cm = CosineAnnealingWarmupRestarts(self.epochs, cfg["SOLVER"]["CM_LR"], 1e-8, warm) if self.use_cm else None
         self.opt.lr = self.schd.lr
@@ -828,14 +864,39 @@ class Trainer:
             out["cm"] = cm_loss.detach()
         idx = self._reduce_and_pack(last)
         scale = 1.0 / self.world
-        self.opt.step(idx, scale)
+        guard = self._decide_grad_guard(idx, out)
+        self.opt.step(idx, scale, guard)
         if compute_ssl:
-            self.opt_ssl.step(idx, scale)
+            self.opt_ssl.step(idx, scale, guard)
         if compute_cm:
-            self.opt_cm.step(idx, scale)
+            self.opt_cm.step(idx, scale, guard)
         Fn.bump_param_epoch()
         self._post_guard()
         return out
+
+    # -- gradient guard ---------------------------------------------------------------------------------------------------
+    def _decide_grad_guard(self, idx: List[int], out: dict):
+        """Guard on: the step's ONE decision, from the reduced gradient runs of `idx` (sum-of-squares passes + finalize, no host
+        sync); returns the device tensor the optimiser kernels read and puts "grad_norm" into the step's result.  Guard off:
+        None, and nothing is launched."""
+        gg = self.grad_guard
+        if gg is None:
+            return None
+        key = tuple(idx)                     # (the runs of a parameter set are computed once: ~250 parameters of Python per call)
+        if self._guard_runs is None or self._guard_runs[0] != key:
+            self._guard_runs = (key, [self.flat.grads[s:e] for s, e, _ in self.flat.runs(idx, lambda i: 0)])
+        guard = gg.decide(self._guard_runs[1], pre_scale=1.0 / self.world)
+        out["grad_norm"] = guard[1]          # a view: read it before the next step overwrites it
+        return guard
+
+    def grad_guard_stats(self) -> Dict[str, float]:
+        """Host values of the guard: the last step's norm (of the averaged gradient) and clip coefficient, and the cumulative
+        numbers of skipped and clipped steps.  Reading synchronises, like reading a loss."""
+        if self.grad_guard is None:
+            raise RuntimeError("Trainer.grad_guard_stats: the gradient guard is off (max_grad_norm / skip_nonfinite)")
+        g = self.grad_guard.guard.tolist()
+        c = self.grad_guard.counters.tolist()
+        return {"norm": g[1], "coef": g[0], "skipped": int(c[0]), "clipped": int(c[1])}
 
     # -- captured graphs: lookup by capacity, capture at size classes -------------------------------------------------------
     _INF = 1 << 60
@@ -914,11 +975,15 @@ class Trainer:
         if self.world > 1 and not g.reduced:
             idx = self._agreed(g.last, idx)
             self._all_reduce_runs(idx)
-        self.opt.step(idx, 1.0 / self.world)
+        guard = None
+        if self.grad_guard is not None:
+            out = dict(out)                  # (the graph's own result dict stays as captured)
+            guard = self._decide_grad_guard(idx, out)
+        self.opt.step(idx, 1.0 / self.world, guard)
         if "ssl" in kind:
-            self.opt_ssl.step(idx, 1.0 / self.world)
+            self.opt_ssl.step(idx, 1.0 / self.world, guard)
         if "cm" in kind:
-            self.opt_cm.step(idx, 1.0 / self.world)
+            self.opt_cm.step(idx, 1.0 / self.world, guard)
         Fn.bump_param_epoch()
         self._post_guard()
         self._replays_since_sync += 1
@@ -1184,14 +1249,20 @@ class Trainer:
         for ep in range(1, epochs + 1):
             sums: Dict[str, torch.Tensor] = {}
             steps = 0
+            guard_before = self.grad_guard.counters.clone() if self.grad_guard is not None else None
             for batch, meta in train_batches():
                 out = self.training_step(batch, meta=meta, cur_epoch=ep)
                 for k, v in out.items():                 # device-side running sums: no host synchronisation per step
+                    if k == "grad_norm":
+                        continue
                     sums[k] = sums[k] + v.detach().float() if k in sums else v.detach().float().clone()
                 steps += 1
             self.on_train_epoch_end(ep)
             val = self.evaluate(val_batches() if callable(val_batches) else val_batches)
             val.update(self._epoch_losses(sums, steps))
+            if guard_before is not None:                 # (the epoch boundary has synchronised already: check_device_flags)
+                skipped, clipped = (self.grad_guard.counters - guard_before).tolist()
+                val.update(grad_skipped=int(skipped), grad_clipped=int(clipped))
             history.append(val)
             if on_epoch is not None:
                 on_epoch(ep, val)

@@ -871,6 +871,41 @@ int dl_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   float grad_scale, void* param_lowp, int32_t lowp_dtype, dl_stream s);
 
 /* ------------------------------------------------------------------------------------------
+ * Gradient guard: global-norm clipping and the non-finite step skip, decided on the device (the host never reads
+ * the norm; the optimiser kernel reads the decision).  Per step: dl_grad_sqnorm once per contiguous gradient run (the
+ * first with accumulate = 0), dl_grad_guard_finalize once, dl_adamw_step_guarded for every optimiser launch.
+ *
+ * dl_grad_sqnorm: acc[0] = (accumulate ? acc[0] : 0) + sum_i g[i]^2 over n fp32 values, n > 0 arbitrary, g 16-byte
+ *   aligned, acc and workspace 8-byte aligned.  Every square and every sum is fp64 (the square of an fp32 value is exact
+ *   in fp64 and never overflows it), so a gradient of finite values gives a finite sum whatever its magnitude, and a NaN
+ *   or an infinity anywhere gives a non-finite sum.  No atomics: one partial per workgroup stored into the workspace, a
+ *   one-workgroup second launch sums them in a fixed order; the result is a function of the values, n and accumulate
+ *   alone, and two calls agree bit for bit.  The relative error against the exact sum is at most n * 2^-53.
+ *   workspace_bytes >= 8 * min(2048, ceil(n / 4096)) (fewer are used for some n; the contents need no initialisation
+ *   and mean nothing afterwards).
+ * dl_grad_guard_finalize (one thread): with norm = pre_scale * sqrt(acc[0]) in fp64 and nonfinite = !isfinite(acc[0]),
+ *   skip     = nonfinite && skip_nonfinite
+ *   coef     = max_norm <= 0 ? 1 : min(1, max_norm / (norm + 1e-6)) in fp64 (torch.nn.utils.clip_grad_norm_; a NaN norm
+ *              gives a NaN coefficient, as torch's clamp does with error_if_nonfinite=False)
+ *   guard[0] = skip ? 0 : (float)coef      guard[1] = (float)norm (may round to +inf for a finite gradient; coef does not)
+ *   guard[2] = skip ? 1 : 0                guard[3] = 0 (reserved)
+ *   counters[0] += skip                    counters[1] += (coef < 1 && !skip)       (cumulative, owned by the caller)
+ *   guard: 4 floats, 16-byte aligned; counters: 2 int64; acc 8-byte aligned.
+ * dl_adamw_step_guarded: dl_adamw_step with the gradient scale (float)(grad_scale * guard[0]) — the same arithmetic, the
+ *   same bits as dl_adamw_step called with that scale — and when guard[2] != 0 nothing is written: param, exp_avg,
+ *   exp_avg_sq and param_lowp keep their bits.  The host-side step count is the caller's business either way.
+ * All three: null pointers, n <= 0, step < 1, a misaligned pointer and a workspace that is too small return DL_ERR_ARG
+ * before anything is launched.
+ * ------------------------------------------------------------------------------------------ */
+int dl_grad_sqnorm(const float* g, int64_t n, double* acc, int32_t accumulate, void* workspace, int64_t workspace_bytes,
+                   dl_stream s);
+int dl_grad_guard_finalize(const double* acc, float pre_scale, float max_norm, int32_t skip_nonfinite, float* guard,
+                           int64_t* counters, dl_stream s);
+int dl_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                          float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                          float grad_scale, void* param_lowp, int32_t lowp_dtype, const float* guard, dl_stream s);
+
+/* ------------------------------------------------------------------------------------------
  * Kernel timing hooks used by bench.py for the roofline object: when enabled for a kernel
  * family, launches are bracketed by hipEventRecord on their own stream.
  * family: 0 gemm, 1 attn_fwd, 2 attn_bwd, 3 layernorm, 4 (unused since round 4), 5 ntxent_fwd, 6 ntxent_bwd.
