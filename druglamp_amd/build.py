@@ -79,8 +79,9 @@ def _stale(out, deps):
 # A/B build (DL_BUILD_NOSLP_FILES=norm.hip,elementwise.hip), without it: the choice is caution, not a failing test.
 # grad_guard.hip gets the flag: its guarded AdamW kernel is elementwise.hip's arithmetic (csrc/adamw.cuh), and the two must give
 # the same bits.
+# ema.hip gets the flag: per-element fp32 on 16-byte vectors, HBM-bound (the packed forms buy nothing) — bn_eval.hip's caution.
 FILE_FLAGS = {"norm.hip": ["-fno-slp-vectorize"], "elementwise.hip": ["-fno-slp-vectorize"], "bn_eval.hip": ["-fno-slp-vectorize"],
-              "grad_guard.hip": ["-fno-slp-vectorize"]}
+              "grad_guard.hip": ["-fno-slp-vectorize"], "ema.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src, force, objdir=OBJDIR, extra=()):

@@ -941,6 +941,29 @@ class GradGuard:
         return self.guard
 
 
+# ---- weight EMA (csrc/ema.hip): a shadow of the parameter arena moved towards the live parameters -----------------------
+def ema_update(ema, param, weight: float, guard=None):
+    """ema += weight * (param - ema) in place, fp32, lerp form (ema == param is a bitwise fixed point); param is not written.
+    guard (ops.GradGuard.guard or None): nothing is written when guard[2] != 0.  Alignment, the weight's range [0, 1], empty
+    and aliased operands are checked by the entry point (RuntimeError through `check`, nothing launched)."""
+    _need_gpu(ema, param, guard)
+    for name, t in (("ema", ema), ("param", param), ("guard", guard)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise TypeError("ema_update: %s must be float32 (got %s)" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("ema_update: %s must be contiguous" % name)
+        if t.device != ema.device:
+            raise ValueError("ema_update: %s is on %s, ema on %s" % (name, t.device, ema.device))
+    if ema.numel() != param.numel():
+        raise ValueError("ema_update: ema has %d elements, param %d" % (ema.numel(), param.numel()))
+    if guard is not None and guard.numel() < 4:
+        raise ValueError("ema_update: guard must hold 4 floats (got %d)" % guard.numel())
+    check(_lib.lib().dl_ema_update(ema.data_ptr(), param.data_ptr(), ema.numel(), float(weight), _ptr(guard), _stream()),
+          "dl_ema_update")
+
+
 def cos_rowloss_fwd(x, y):
     n, D = x.shape
     row = torch.empty(n, dtype=torch.float32, device=x.device)

@@ -21,11 +21,14 @@ What is new (MI355X-native):
   * a backward pass whose gradients the next zero_grad wipes before any optimiser steps (cls on SSL / CM
     steps, ssl on CM steps) is not run: the parameters after the step are the same, the step is shorter;
   * optional gradient guard (Trainer(max_grad_norm=..., skip_nonfinite=...)): global-norm clipping and the skip of a step with
-    a non-finite gradient, decided on the device from one fp64 pass over the flat gradient — no host round trip.
+    a non-finite gradient, decided on the device from one fp64 pass over the flat gradient — no host round trip;
+  * optional weight EMA (Trainer(ema_decay=...), WeightEMA): an averaged copy of the arena, one dl_ema_update pass per step behind
+    the last optimiser, swapped in for evaluation and screening (Trainer.ema_weights) or for good (Trainer.adopt_ema).
 """
 from __future__ import annotations
 
 import collections
+import contextlib
 import math
 import os
 from typing import Dict, List, Optional, Sequence
@@ -242,6 +245,32 @@ class FusedAdamW:
             self.steps[i] += 1
 
 
+class WeightEMA:
+    """An exponential moving average of the parameters on a FlatParams: `shadow`, an fp32 clone of the arena taken at
+    construction (timm's ModelEmaV2; torch's AveragedModel after its first update_parameters), moved towards the arena by ONE
+    dl_ema_update launch over the WHOLE arena per training step — parameters that received no gradient this step are averaged
+    too (towards their unchanged value), as standard EMA does, and equal values (those, and the arena's padding) keep their bits.
+    Weight of the update after t earlier ones: 1 - decay, or with warmup 1 - min(decay, (1 + t) / (10 + t)) — without it a
+    short fine-tune never leaves its initial weights; the kernel receives the weight rounded to fp32.
+    `updates` is a host count.  Like FusedAdamW's step counts it advances on a step the gradient guard skipped (the kernel
+    writes nothing then, but the host does not know the device's decision), so the warmup schedule counts skipped steps."""
+
+    def __init__(self, flat: FlatParams, decay: float, warmup: bool = False):
+        self.flat, self.decay, self.warmup = flat, float(decay), bool(warmup)
+        self.shadow = flat.arena.clone()
+        self.updates = 0
+
+    def weight(self, t: Optional[int] = None) -> float:
+        """The weight of the update that follows t earlier ones (default: the next one), before its rounding to fp32."""
+        t = self.updates if t is None else t
+        return 1.0 - (min(self.decay, (1.0 + t) / (10.0 + t)) if self.warmup else self.decay)
+
+    def update(self, guard: Optional[torch.Tensor] = None):
+        """guard (ops.GradGuard.guard): nothing is written when guard[2] != 0; `updates` advances either way."""
+        ops.ema_update(self.shadow, self.flat.arena, self.weight(), guard)
+        self.updates += 1
+
+
 class GraphedStep:
     """The cls-only part of a training step — forward, BCE, backward, gradient packing — captured ONCE per batch shape
     into a hipGraph (torch.cuda.CUDAGraph drives hipStreamBeginCapture on a side stream; every libdruglamp_hip launch
@@ -249,8 +278,9 @@ class GraphedStep:
     in the graph) and replayed with one host call per step.  At 32-64 pairs per GPU the eager step is bound by the
     7-9 ms the host needs to enqueue it; the replay costs the host < 1 ms.
 
-    What stays outside the graph, on purpose: the gradient all-reduce (RCCL) and the fused AdamW launches (their step
-    counts and learning rates are by-value arguments that change from step to step).
+    What stays outside the graph, on purpose: the gradient all-reduce (RCCL), the fused AdamW launches (their step
+    counts and learning rates are by-value arguments that change from step to step) and the weight-EMA pass behind them (its
+    weight is one too).
     What makes a replay a NEW step although every launch argument is frozen:
       * inputs are copied into the graph's static input tensors (skipped when the caller hands over those very
         tensors, Trainer.static_batch — a loader can assemble the next batch in place);
@@ -459,9 +489,13 @@ class Trainer:
     _agreed_sets = None
     grad_bf16 = False
     graph_allreduce = False
+    ema = None
+    _ema_spare = None
+    _ema_swapped = False
 
     def __init__(self, model, cfg, device=None, compute_dtype=torch.float32, graph_steps: bool = False, freeze_bn: bool = False,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = False):
         """freeze_bn=True: fine-tuning with frozen BatchNorm (model.freeze_batchnorm()): every BatchNorm1d normalises with its
         running statistics, which the steps leave bitwise unchanged; its weight / bias train.  cls steps only (eager or
         replayed): with the SSL or the CM head switched on (RS.SSL / RS.CM) construction raises.
@@ -479,7 +513,21 @@ class Trainer:
             ones — unlike torch.cuda.amp.GradScaler, which does not count a skipped step; the price of a step that never
             waits for the device.  BatchNorm running statistics are updated by the forward pass and are outside the
             guard's reach: a forward that produced non-finite activations has already written them.
-        The step's result gains "grad_norm" (a device scalar); grad_guard_stats() reads the counters."""
+        The step's result gains "grad_norm" (a device scalar); grad_guard_stats() reads the counters.
+
+        ema_decay / ema_warmup: the weight EMA (off unless ema_decay is set: `ema` is None, nothing is allocated and a step
+        launches exactly what it launches without it).  ema_decay: a float in [0, 1).  On, `ema` is a WeightEMA whose shadow
+        starts as a clone of the arena (after the replicas were synchronised) and every training step — eager or replayed —
+        ends with one dl_ema_update over the whole arena behind its last optimiser, outside the captured graph, reading the
+        step's guard when the gradient guard is on: a skipped step leaves the shadow's bits alone.  As with the
+        per-parameter step counts above, `ema.updates` advances on a skipped step all the same, and with ema_warmup the
+        weight schedule counts it.  The shadow is a function of bit-identical parameters and a bit-identical guard decision
+        on every rank: replicas hold the same shadow without another collective.  ema_weights() / adopt_ema() put the
+        average to use; fit() validates and selects on it.  Buffers (BatchNorm running statistics) are shared, not averaged."""
+        if ema_decay is not None:
+            ok = isinstance(ema_decay, (int, float)) and not isinstance(ema_decay, bool) and 0.0 <= float(ema_decay) < 1.0
+            if not ok:
+                raise ValueError("Trainer(ema_decay=%r): must be None or a float in [0, 1)" % (ema_decay,))
         if max_grad_norm is not None:
             mg = float(max_grad_norm)
             if not (mg > 0.0 and math.isfinite(mg)):
@@ -522,6 +570,8 @@ class Trainer:
         if self.max_grad_norm is not None or self.skip_nonfinite:
             self.grad_guard = ops.GradGuard(self.flat.numel, self.flat.grads.device, max_norm=self.max_grad_norm or 0.0,
                                             skip_nonfinite=self.skip_nonfinite)
+        if ema_decay is not None:
+            self.ema = WeightEMA(self.flat, float(ema_decay), warmup=ema_warmup)
         self.schd =CosineAnnealingWarmupRestarts(self.epochs, cfg["SOLVER"]["LR"], 1e-8, warm)
         self.schd_ssl = CosineAnnealingWarmupRestarts(self.epochs, cfg["SOLVER"]["SSL_LR"], 1e-8, warm) if self.use_ssl else None
         self.schd_cm = CosineAnnealingWarmupRestarts(self.epochs, cfg["SOLVER"]["CM_LR"], 1e-8, warm) if self.use_cm else None
@@ -589,21 +639,29 @@ class Trainer:
 
     # -- helpers ------------------------------------------------------------------------------------
     def sync_replicas(self, src: int = 0):
-        """Broadcast the parameter arena and every module buffer from rank `src` (no-op at world size 1)."""
+        """Broadcast the parameter arena, the EMA shadow (where there is one) and every module buffer from rank `src` (no-op at
+        world size 1)."""
         if self.world <= 1:
             return
         dist.broadcast(self.flat.arena, src=src)
+        if self.ema is not None:
+            dist.broadcast(self.ema.shadow, src=src)
         for b in self.model.buffers():
             dist.broadcast(b, src=src)
         Fn.bump_param_epoch()
 
     def replicas_in_sync(self) -> bool:
-        """True iff every rank holds bit-identical parameters (a cheap checksum all-gather; used by tests / on demand)."""
+        """True iff every rank holds bit-identical parameters — and, with the weight EMA on, a bit-identical shadow (a cheap
+        checksum all-gather; used by tests / on demand)."""
         if self.world <= 1:
             return True
-        a = self.flat.arena
-        chk = torch.stack((a.double().sum(), a.double().abs().sum(), (a.double() * torch.arange(1, a.numel() + 1, device=a.device,
-                                                                                                   dtype=torch.float64) % 9973).sum()))
+
+        def checksum(a):
+            return torch.stack((a.double().sum(), a.double().abs().sum(), (a.double() * torch.arange(1, a.numel() + 1, device=a.device,
+                                                                                                      dtype=torch.float64) % 9973).sum()))
+        chk = checksum(self.flat.arena)
+        if self.ema is not None:
+            chk = torch.cat((chk, checksum(self.ema.shadow)))
         allc = [torch.empty_like(chk) for _ in range(self.world)]
         dist.all_gather(allc, chk)
         return all(torch.equal(allc[0], c) for c in allc[1:])
@@ -784,6 +842,8 @@ class Trainer:
         cur_epoch is 1-based (trainer.py:180).  Returns the losses as detached DEVICE scalars ({'cls': ..., 'ssl': ..., 'cm': ...}): the
         step itself never synchronises with the host (reading a value does), so steps are enqueued back to back."""
         m = self.model
+        if self._ema_swapped:
+            raise RuntimeError("Trainer.training_step inside ema_weights(): the arena holds the averaged weights")
         self._poll_guard()
         if not m.training:
             m.train()                  # (walks every submodule: 0.7 ms per call)
@@ -870,6 +930,8 @@ class Trainer:
             self.opt_ssl.step(idx, scale, guard)
         if compute_cm:
             self.opt_cm.step(idx, scale, guard)
+        if self.ema is not None:
+            self.ema.update(guard)
         Fn.bump_param_epoch()
         self._post_guard()
         return out
@@ -897,6 +959,46 @@ class Trainer:
         g = self.grad_guard.guard.tolist()
         c = self.grad_guard.counters.tolist()
         return {"norm": g[1], "coef": g[0], "skipped": int(c[0]), "clipped": int(c[1])}
+
+    # -- weight EMA -------------------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the parameter arena holds the averaged weights (the live bits wait in a spare buffer); on exit,
+        exceptions included, the live bits are back.  The parameter epoch is bumped both ways, so predict, evaluate, screen,
+        build_library, screen_library and hit_* work unchanged on the averaged weights: weight images are refreshed, codes
+        and libraries built inside are stale outside (the existing parameter-epoch check), and a library built inside carries
+        the fingerprint of the averaged weights.  Buffers — BatchNorm running statistics among them — are SHARED with the live
+        model, not averaged (torch.optim.swa_utils.AveragedModel's default, use_buffers=False).  Entering twice raises, and
+        so does training_step inside the context."""
+        if self.ema is None:
+            raise RuntimeError("Trainer.ema_weights: the weight EMA is off (ema_decay)")
+        if self._ema_swapped:
+            raise RuntimeError("Trainer.ema_weights: already inside ema_weights()")
+        if self._ema_spare is None:
+            self._ema_spare = torch.empty_like(self.flat.arena)
+        with torch.no_grad():
+            self._ema_spare.copy_(self.flat.arena)
+            self.flat.arena.copy_(self.ema.shadow)
+        self._ema_swapped = True
+        Fn.bump_param_epoch()
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                self.flat.arena.copy_(self._ema_spare)
+            self._ema_swapped = False
+            Fn.bump_param_epoch()
+
+    def adopt_ema(self):
+        """Copy the averaged weights into the live arena for good (model.state_dict() then holds them: deployment) and bump
+        the parameter epoch.  The optimisers' moments are left as they are."""
+        if self.ema is None:
+            raise RuntimeError("Trainer.adopt_ema: the weight EMA is off (ema_decay)")
+        if self._ema_swapped:
+            raise RuntimeError("Trainer.adopt_ema inside ema_weights(): the exit would put the live weights back")
+        with torch.no_grad():
+            self.flat.arena.copy_(self.ema.shadow)
+        Fn.bump_param_epoch()
 
     # -- captured graphs: lookup by capacity, capture at size classes -------------------------------------------------------
     _INF = 1 << 60
@@ -984,6 +1086,8 @@ class Trainer:
             self.opt_ssl.step(idx, 1.0 / self.world, guard)
         if "cm" in kind:
             self.opt_cm.step(idx, 1.0 / self.world, guard)
+        if self.ema is not None:
+            self.ema.update(guard)
         Fn.bump_param_epoch()
         self._post_guard()
         self._replays_since_sync += 1
@@ -1241,10 +1345,13 @@ class Trainer:
         (a callable yielding (batch, meta) pairs), on_train_epoch_end, validation; the parameters with the best
         `val_ausum` (AUROC + AUPRC: ModelCheckpoint(monitor='val_ausum', mode='max')) are kept, training stops after
         patience = epochs / 4 epochs without improvement (EarlyStopping, min_delta 0), and the best parameters are
-        reloaded before returning (trainer.py:134) — ready for evaluate(test_batches)."""
+        reloaded before returning (trainer.py:134) — ready for evaluate(test_batches).
+        With the weight EMA on, validation runs under ema_weights() (selection and early stopping judge the averaged weights),
+        every history entry says so ("weights": "ema"), and the best snapshot holds the live arena, the shadow and the
+        buffers: all three are reloaded."""
         epochs = int(epochs or self.epochs)
         patience = max(int(epochs / 4), 1)
-        best = {"ausum": -float("inf"), "epoch": 0, "arena": None, "buffers": None}
+        best = {"ausum": -float("inf"), "epoch": 0, "arena": None, "buffers": None, "shadow": None}
         history, bad = [], 0
         for ep in range(1, epochs + 1):
             sums: Dict[str, torch.Tensor] = {}
@@ -1258,7 +1365,12 @@ class Trainer:
                     sums[k] = sums[k] + v.detach().float() if k in sums else v.detach().float().clone()
                 steps += 1
             self.on_train_epoch_end(ep)
-            val = self.evaluate(val_batches() if callable(val_batches) else val_batches)
+            if self.ema is not None:
+                with self.ema_weights():
+                    val = self.evaluate(val_batches() if callable(val_batches) else val_batches)
+                val["weights"] = "ema"
+            else:
+                val = self.evaluate(val_batches() if callable(val_batches) else val_batches)
             val.update(self._epoch_losses(sums, steps))
             if guard_before is not None:                 # (the epoch boundary has synchronised already: check_device_flags)
                 skipped, clipped = (self.grad_guard.counters - guard_before).tolist()
@@ -1269,7 +1381,8 @@ class Trainer:
             score = val["ausum"]
             if score == score and score > best["ausum"]:
                 best.update(ausum=score, epoch=ep, arena=self.flat.arena.clone(),
-                            buffers=[b.detach().clone() for b in self.model.buffers()])
+                            buffers=[b.detach().clone() for b in self.model.buffers()],
+                            shadow=self.ema.shadow.clone() if self.ema is not None else None)
                 bad = 0
             else:
                 bad += 1
@@ -1278,6 +1391,8 @@ class Trainer:
         if best["arena"] is not None:                                    # reload the best checkpoint (trainer.py:134)
             with torch.no_grad():
                 self.flat.arena.copy_(best["arena"])
+                if best["shadow"] is not None:
+                    self.ema.shadow.copy_(best["shadow"])
                 for b, src in zip(self.model.buffers(), best["buffers"]):
                     b.copy_(src)
             Fn.bump_param_epoch()

@@ -906,6 +906,26 @@ int dl_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float
                           float grad_scale, void* param_lowp, int32_t lowp_dtype, const float* guard, dl_stream s);
 
 /* ------------------------------------------------------------------------------------------
+ * Weight EMA: a shadow copy of the flat parameter arena moved towards the live parameters, one pass per training step.
+ *
+ * dl_ema_update: for every i < n, in fp32,
+ *     d = param[i] - ema[i];   ema[i] = (d == 0) ? ema[i] : fmaf(weight, d, ema[i])
+ *   — the lerp form e + w (p - e): one rounding of the difference, one of the fma, so |result - exact| <=
+ *   3 * 2^-24 * max(|ema[i]|, |param[i]|) for weight in [0, 1].  ema[i] == param[i] is a fixed point BIT FOR BIT for any
+ *   weight (parameters that received no gradient and arena padding keep their bits); the explicit d == 0 case is what
+ *   extends that to a pair of negative zeros, where the fma alone would give +0.  param is never written.
+ *   guard: null, or the 16-byte {coef, norm, skip, 0} record of dl_grad_guard_finalize; when guard[2] != 0 nothing is
+ *   written (one 16-byte load at a wave-uniform address, return before any other access, as dl_adamw_step_guarded).
+ *   Non-finite values pass through as the arithmetic says: a NaN parameter makes that element NaN, +-inf against a finite
+ *   average makes +-inf (NaN at weight 0: 0 * inf), inf against the same inf makes NaN (inf - inf).
+ *   16-byte loads and stores with a scalar tail for n % 4; one 16-byte chunk per thread, the grid a function of n alone; no
+ *   atomics, no LDS: two calls on the same data agree bit for bit.
+ *   DL_ERR_ARG before anything is launched: null ema or param, n <= 0, ema / param / guard not 16-byte aligned, weight not
+ *   a finite value in [0, 1], ema == param.
+ * ------------------------------------------------------------------------------------------ */
+int dl_ema_update(float* ema, const float* param, int64_t n, float weight, const float* guard, dl_stream s);
+
+/* ------------------------------------------------------------------------------------------
  * Kernel timing hooks used by bench.py for the roofline object: when enabled for a kernel
  * family, launches are bracketed by hipEventRecord on their own stream.
  * family: 0 gemm, 1 attn_fwd, 2 attn_bwd, 3 layernorm, 4 (unused since round 4), 5 ntxent_fwd, 6 ntxent_bwd.
