@@ -62,10 +62,10 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_lse_kernel(const ProbsP p
   const T* Qb = reinterpret_cast<const T*>(p.Q) + (int64_t)qprob * p.q_ps + (int64_t)h * p.q_hs;
   const T* Kb = reinterpret_cast<const T*>(p.K) + (int64_t)pr * p.k_ps + (int64_t)h * p.k_hs;
   const int q = qb * 64 + wave * 16 + il;
-  u32x4 qf[NKF];
+  u32x4 qf[1][NKF];                                     // (QT = 1 forms of the arrays the tile steps of tiles.cuh take)
 #pragma unroll
-  for (int kf = 0; kf < NKF; ++kf) qf[kf] = frag_global<T>(Qb + (int64_t)q * p.q_rs, q < p.Lq, kf, g);
-  float m_run = -INFINITY, l_run = 0.f;
+  for (int kf = 0; kf < NKF; ++kf) qf[0][kf] = frag_global<T>(Qb + (int64_t)q * p.q_rs, q < p.Lq, kf, g);
+  float m_run[1] = {-INFINITY}, l_run[1] = {0.f};
   const float c = p.scale * LOG2E;
   const int nt = (p.Lk + KVB - 1) / KVB;
   dma_rows<T, HD, ATT_THREADS>(smem, Kb, p.k_rs, p.Lk, KVB);
@@ -75,37 +75,13 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_lse_kernel(const ProbsP p
     __syncthreads();                                    // barrier covers LDS only); then: tile t has landed, the other buffer is free
     if (t + 1 < nt)
       dma_rows<T, HD, ATT_THREADS>(smem + ((t + 1) & 1) * BUF, Kb + (int64_t)(k0 + KVB) * p.k_rs, p.k_rs, p.Lk - k0 - KVB, KVB);
-    f32x4 s[NKT];
-    score_tile<T, HD>(smem + (t & 1) * BUF, qf, s, il, g);
-    if (k0 + KVB > p.tail_start || k0 + KVB > p.Lk) {
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int key = k0 + kt * 16 + 4 * g + r;
-          if (key >= p.tail_start) s[kt][r] += p.tail_bias;
-          if (key >= p.Lk) s[kt][r] = -INFINITY;
-        }
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kt][r]);
-    mx = group4_max(mx);
-    const float m_new = fmaxf(m_run, mx);
-    const float alpha = fast_exp2((m_run - m_new) * c);
-    const float mc = m_new * c;
-    float rs = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) rs += fast_exp2(s[kt][r] * c - mc);
-    l_run = l_run * alpha + rs;                         // per-lane partial (own keys); reduced at the end
-    m_run = m_new;
+    f32x4 s[1][NKT];
+    score_tile<T, HD>(smem + (t & 1) * BUF, qf[0], s[0], il, g);
+    mask_keys(s, k0, p.Lk, p.tail_start, p.tail_bias, g);
+    sweep_stats(s, m_run, l_run, c);
   }
-  const float l = group4_sum(l_run);
-  if (q < p.Lq && g == 0) p.LSE_out[(((int64_t)seg * p.P + pr) * p.H + h) * p.Lq + q] = m_run * p.scale + logf(l);
+  const float l = group4_sum(l_run[0]);
+  if (q < p.Lq && g == 0) p.LSE_out[(((int64_t)seg * p.P + pr) * p.H + h) * p.Lq + q] = m_run[0] * p.scale + logf(l);
 }
 
 // =================================== probabilities =============================================

@@ -5,12 +5,8 @@
 //   Pair n reads its queries from entity q_index[n] of Q and its keys / values from the segment of K / V that entity
 //   kv_index[n] owns: the operands are the cached per-entity codes (druglamp_amd/screening.py), nothing is gathered per pair.
 //   Where that segment lies is the one thing the two entry points differ in, and the kernel takes it from its `Keys` type
-//   (pair_keys.cuh, shared with the probability maps of pgca_pairs_probs.hip):
-//     DenseKeys  : entity d of K / V, k_es / v_es elements apart; Lk, the tail rows and their weight are launch-wide.
-//     RaggedKeys : rows kv_row0[d] .. kv_row0[d] + kv_keys[d] - 1 of one packed [K | V'] row store, whose last key_tail_rows
-//                  rows stand for kv_tail_weight[d] identical keys each (DrugLibrary); the table entry is read at the top of
-//                  the workgroup (scalar loads: the entry's index is a scalar load itself).  The workgroups of a short drug
-//                  run fewer tiles; rows >= Lk of the last tile read the zero page, never the next drug's rows.
+//   (pair_keys.cuh).  The workgroups of a short drug run fewer tiles; rows >= Lk of the last tile read the zero page, never the
+//   next drug's rows.
 //
 //   pgca_pairs_kernel : one workgroup owns 64 * QT query rows of one pair; a wave owns 16 * QT of them.  The arithmetic is
 //                       attention.hip's streamed forward (the three tile steps of tiles.cuh): 64-key tiles of K and V pass
@@ -29,7 +25,7 @@
 
 namespace {
 using namespace dltile;
-using namespace dlpairs;       // KeySeg, DenseKeys, RaggedKeys: shared with pgca_pairs_probs.hip
+using namespace dlpairs;
 
 // the part of the launch that does not depend on where a pair's keys lie
 struct PairsCommon {
@@ -48,13 +44,11 @@ template <typename Keys> struct PairsP : PairsCommon {
   Keys keys;
 };
 
-constexpr int KVB = 64;            // keys per streamed tile
-
 // LDS: two (K tile, V tile) pairs = 64 KB in bf16 (two workgroups per CU), 128 KB in fp32 (one: the parity dtype)
 template <typename T, int HD, int QT, typename Keys>
 __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP<Keys> p) {
   using TL = ATile<T, HD>;
-  constexpr int NKF = HD / Mma<T>::KF, NDT = HD / 16, NKT = KVB / 16;
+  constexpr int NKF = HD / Mma<T>::KF, NDT = HD / 16;
   constexpr int QB = 4 * QT * 16;
   constexpr int BUF = 2 * KVB * TL::RB;                 // one (K tile, V tile) pair
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
@@ -62,14 +56,10 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, il = lane & 15, g = lane >> 4;
   const int n = blockIdx.x / p.bps, qb = blockIdx.x % p.bps;
   const int pi = p.qi[n], di = p.ki[n];
-  // Both guards are uniform for the workgroup: the indices and what locate() reads are scalar loads (the keys' entry is read
-  // only through an index in range; all of them in front of the one atomic, so that nothing the compiler must treat as a
-  // store precedes them).
   KeySeg ks = {};
-  const bool in_range = (unsigned)pi < (unsigned)p.n_q && (unsigned)di < (unsigned)p.n_kv;
-  const uint32_t bad = in_range ? p.keys.locate(di, p.k_rs, p.v_rs, p.scale, ks) : (uint32_t)DL_FLAG_PAIR_INDEX;
-  if (bad) {                                            // the pair is skipped: nothing read through the entry, nothing written
-    if (p.flags && qb == 0 && threadIdx.x == 0) atomicOr(p.flags, bad);
+  const uint32_t bad = pair_guard(p, pi, di, p.v_rs, ks);
+  if (bad) {
+    flag_pair(p.flags, bad, qb == 0 && threadIdx.x == 0);
     return;
   }
   const int Lk = ks.Lk, tail_start = ks.tail_start;
@@ -81,12 +71,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP
 
   const int qw0 = qb * QB + wave * QT * 16;
   u32x4 qf[QT][NKF];
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    const int q = qw0 + qt * 16 + il;
-#pragma unroll
-    for (int kf = 0; kf < NKF; ++kf) qf[qt][kf] = frag_global<T>(Qb + (int64_t)q * p.q_rs, q < p.Lq, kf, g);
-  }
+  load_q_frags(qf, Qb, p.q_rs, qw0, p.Lq, il, g);
 
   f32x4 o[NDT][QT];
 #pragma unroll
@@ -127,20 +112,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP
     const char* Vs = Ks + KVB * TL::RB;
     f32x4 s[QT][NKT];
     fwd_scores<T, HD>(Ks, qf, s, il, g);                // S^T = K Q^T
-    // ---- key multiplicities, key masking (tiles in front of both skip this through a uniform branch) ----
-    if (k0 + KVB > tail_start || k0 + KVB > Lk) {
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int key = k0 + kt * 16 + 4 * g + r;
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt) {
-            if (key >= tail_start) s[qt][kt][r] += tail_bias;
-            if (key >= Lk) s[qt][kt][r] = -INFINITY;
-          }
-        }
-    }
+    mask_keys(s, k0, Lk, tail_start, tail_bias, g);     // key multiplicities, key masking
     fwd_softmax(s, m_run, l_run, o, c);                 // online maximum / sum, rescale of o
     fwd_accumulate<T, HD>(Vs, s, o, il, g);             // O^T += V^T P^T
     // (no barrier here: the one at the top of the next iteration is what separates this tile's reads from the DMA that
@@ -164,26 +136,17 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_kernel(const PairsP
   }
 }
 
-template <typename T> constexpr int pairs_qt() { return sizeof(T) == 2 ? 2 : 1; }
-
 template <typename Keys>
 void launch_pairs(int dtype, const PairsP<Keys>& p, int n_pairs, hipStream_t s) {
-  const dim3 grid((uint32_t)n_pairs * (uint32_t)p.bps);
-  if (dtype == DL_BF16) hipLaunchKernelGGL((pgca_pairs_kernel<bf16_t, 128, pairs_qt<bf16_t>(), Keys>), grid, dim3(ATT_THREADS), 0, s, p);
-  else hipLaunchKernelGGL((pgca_pairs_kernel<float, 128, pairs_qt<float>(), Keys>), grid, dim3(ATT_THREADS), 0, s, p);
+  launch_by_dtype(dtype, pgca_pairs_kernel<bf16_t, 128, pair_qt<bf16_t>(), Keys>, pgca_pairs_kernel<float, 128, pair_qt<float>(), Keys>,
+                  (uint32_t)n_pairs * (uint32_t)p.bps, ATT_THREADS, s, p);
 }
 
 // What dl_pgca_pairs_args and dl_pgca_pairs_ragged_args share (same field names): the checks, and the common block of the
 // launch.  st / stn: the entry point's strides and their names, left_es and left_rs at st[left_at] and st[left_at + 1].
-// Nothing behind a pointer is looked at, and with n_pairs == 0 (no launch) no pointer or stride either.
 template <typename Args>
 int pairs_common(const char* who, const Args* a, const int64_t* st, const char* const* stn, int n_st, int left_at, PairsCommon& p) {
-  DL_CHECK_ARG(a->dtype == DL_F32 || a->dtype == DL_BF16, DL_ERR_ARG, "%s: bad dtype %d", who, a->dtype);
-  DL_CHECK_ARG(a->head_dim == 128, DL_ERR_UNSUPPORTED, "%s: head_dim %d (one head of 128 only)", who, a->head_dim);
-  DL_CHECK_ARG(a->n_pairs >= 0 && a->n_q >= 0 && a->n_kv >= 0, DL_ERR_SHAPE, "%s: negative count (n_pairs %d, n_q %d, n_kv %d)", who,
-               a->n_pairs, a->n_q, a->n_kv);
-  DL_CHECK_ARG(a->Lq > 0, DL_ERR_SHAPE, "%s: Lq %d must be positive", who, a->Lq);
-  DL_CHECK_ARG(a->scale > 0.f, DL_ERR_ARG, "%s: scale must be positive", who);
+  DL_TRY(pair_head_checks(who, a));
   DL_CHECK_ARG(a->left_cols >= 0 && a->left_cols % 8 == 0, DL_ERR_ALIGN, "%s: left_cols %d not a non-negative multiple of 8 elements", who,
                a->left_cols);
   DL_CHECK_ARG(a->out_col0 >= 0 && a->out_col0 % 8 == 0, DL_ERR_ALIGN, "%s: out_col0 %d not a non-negative multiple of 8 elements", who,
@@ -193,29 +156,20 @@ int pairs_common(const char* who, const Args* a, const int64_t* st, const char* 
                a->left_cols);
   if (a->n_pairs == 0) return DL_OK;
   DL_CHECK_ARG(a->Q && a->K && a->V && a->out && a->q_index && a->kv_index, DL_ERR_ARG, "%s: null pointer (Q, K, V, out, q_index, kv_index)", who);
-  const int epc = 16 / (int)dl_dtype_size(a->dtype);
-  for (int i = 0; i < n_st; ++i) {
-    if (!a->left && (i == left_at || i == left_at + 1)) continue;       // (left_es / left_rs are not read without left)
-    DL_CHECK_ARG(st[i] >= 0 && st[i] % epc == 0, DL_ERR_ALIGN, "%s: stride %s (%ld) not a non-negative multiple of %d elements", who,
-                 stn[i], (long)st[i], epc);
-  }
+  DL_TRY(pair_stride_checks(who, a->dtype, st, stn, n_st, a->left ? -2 : left_at));    // (left_es / left_rs are not read without left)
   DL_CHECK_ARG((((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->V | (uintptr_t)a->out | (uintptr_t)a->left | (uintptr_t)a->bias) & 15) == 0,
                DL_ERR_ALIGN, "%s: Q / K / V / left / out / bias not 16-byte aligned", who);
-  DL_CHECK_ARG((((uintptr_t)a->q_index | (uintptr_t)a->kv_index | (uintptr_t)a->flags) & 3) == 0, DL_ERR_ALIGN,
-               "%s: q_index / kv_index / flags not 4-byte aligned", who);
+  DL_TRY(pair_index_checks(who, a));
   DL_CHECK_ARG(a->out_rs >= (int64_t)a->out_col0 + a->head_dim, DL_ERR_SHAPE, "%s: out_rs %ld below out_col0 + head_dim = %d", who,
                (long)a->out_rs, a->out_col0 + a->head_dim);
-  const int qt = a->dtype == DL_BF16 ? pairs_qt<bf16_t>() : pairs_qt<float>();
-  const int bps = (a->Lq + 64 * qt - 1) / (64 * qt);
-  DL_CHECK_ARG((int64_t)a->n_pairs * bps <= INT32_MAX, DL_ERR_SHAPE, "%s: too many workgroups (%d pairs x %d)", who, a->n_pairs, bps);
-  p.Q = (const char*)a->Q; p.K = (const char*)a->K; p.V = (const char*)a->V; p.left = (const char*)a->left;
-  p.out = (char*)a->out; p.bias = a->bias; p.qi = a->q_index; p.ki = a->kv_index; p.flags = a->flags;
-  p.q_es = a->q_es; p.q_rs = a->q_rs; p.k_rs = a->k_rs; p.v_rs = a->v_rs;
+  DL_TRY(pair_blocks(who, a, p.bps));
+  fill_pair_head(a, p);
+  p.V = (const char*)a->V; p.left = (const char*)a->left;
+  p.out = (char*)a->out; p.bias = a->bias;
+  p.v_rs = a->v_rs;
   p.left_es = a->left_es; p.left_rs = a->left_rs; p.out_ps = a->out_ps; p.out_rs = a->out_rs;
-  p.n_q = a->n_q; p.n_kv = a->n_kv; p.Lq = a->Lq; p.bps = bps;
-  p.left_chunks = a->left ? a->left_cols / epc : 0;
+  p.left_chunks = a->left ? a->left_cols / (16 / (int)dl_dtype_size(a->dtype)) : 0;
   p.out_col0 = a->out_col0;
-  p.scale = a->scale;
   return DL_OK;
 }
 
@@ -223,21 +177,13 @@ int pairs_common(const char* who, const Args* a, const int64_t* st, const char* 
 
 extern "C" int dl_pgca_pairs_fwd(const dl_pgca_pairs_args* a, dl_stream stream) {
   const char* who = "dl_pgca_pairs_fwd";
-  DL_CHECK_ARG(a, DL_ERR_ARG, "%s: null argument block", who);
-  DL_CHECK_ARG(a->Lq > 0 && a->Lk > 0, DL_ERR_SHAPE, "%s: Lq %d, Lk %d must be positive", who, a->Lq, a->Lk);
-  DL_CHECK_ARG(a->key_tail_rows >= 0 && a->key_tail_rows <= a->Lk, DL_ERR_ARG, "%s: key_tail_rows %d not in [0, Lk = %d]", who,
-               a->key_tail_rows, a->Lk);
-  DL_CHECK_ARG(a->key_tail_rows == 0 || a->key_tail_weight >= 1.f, DL_ERR_ARG, "%s: key_tail_weight %g below 1", who,
-               (double)a->key_tail_weight);
+  DL_TRY(dense_head_checks(who, a));
   const int64_t st[] = {a->q_es, a->q_rs, a->k_es, a->k_rs, a->v_es, a->v_rs, a->left_es, a->left_rs, a->out_ps, a->out_rs};
   const char* stn[] = {"q_es", "q_rs", "k_es", "k_rs", "v_es", "v_rs", "left_es", "left_rs", "out_ps", "out_rs"};
   PairsP<DenseKeys> p = {};
   const int rc = pairs_common(who, a, st, stn, 10, 6, p);
   if (rc != DL_OK || a->n_pairs == 0) return rc;
-  p.keys.k_es = a->k_es; p.keys.v_es = a->v_es;
-  p.keys.Lk = a->Lk;
-  p.keys.tail_start = a->Lk - a->key_tail_rows;
-  p.keys.tail_bias = a->key_tail_rows ? logf(a->key_tail_weight) / a->scale : 0.f;
+  fill_dense_keys(a, a->v_es, true, p.keys);
   launch_pairs(a->dtype, p, a->n_pairs, (hipStream_t)stream);
   DL_CHECK_LAUNCH("dl_pgca_pairs_fwd");
   return DL_OK;
@@ -245,21 +191,13 @@ extern "C" int dl_pgca_pairs_fwd(const dl_pgca_pairs_args* a, dl_stream stream) 
 
 extern "C" int dl_pgca_pairs_ragged_fwd(const dl_pgca_pairs_ragged_args* a, dl_stream stream) {
   const char* who = "dl_pgca_pairs_ragged_fwd";
-  DL_CHECK_ARG(a, DL_ERR_ARG, "%s: null argument block", who);
-  DL_CHECK_ARG(a->kv_total_rows >= 0, DL_ERR_SHAPE, "%s: kv_total_rows %ld is negative", who, (long)a->kv_total_rows);
-  DL_CHECK_ARG(a->key_tail_rows >= 0, DL_ERR_ARG, "%s: key_tail_rows %d is negative", who, a->key_tail_rows);
+  DL_TRY(ragged_head_checks(who, a));
   const int64_t st[] = {a->q_es, a->q_rs, a->k_rs, a->v_rs, a->left_es, a->left_rs, a->out_ps, a->out_rs};
   const char* stn[] = {"q_es", "q_rs", "k_rs", "v_rs", "left_es", "left_rs", "out_ps", "out_rs"};
   PairsP<RaggedKeys> p = {};
   const int rc = pairs_common(who, a, st, stn, 8, 4, p);
   if (rc != DL_OK || a->n_pairs == 0) return rc;
-  DL_CHECK_ARG(a->kv_row0 && a->kv_keys && a->kv_tail_weight, DL_ERR_ARG, "%s: null pointer (kv_row0, kv_keys, kv_tail_weight)", who);
-  DL_CHECK_ARG(((uintptr_t)a->kv_row0 & 7) == 0, DL_ERR_ALIGN, "%s: kv_row0 not 8-byte aligned", who);
-  DL_CHECK_ARG((((uintptr_t)a->kv_keys | (uintptr_t)a->kv_tail_weight) & 3) == 0, DL_ERR_ALIGN,
-               "%s: kv_keys / kv_tail_weight not 4-byte aligned", who);
-  p.keys.row0 = a->kv_row0; p.keys.keys = a->kv_keys; p.keys.tailw = a->kv_tail_weight;
-  p.keys.total_rows = a->kv_total_rows;
-  p.keys.tail_rows = a->key_tail_rows;
+  DL_TRY(fill_ragged_keys(who, a, p.keys));
   launch_pairs(a->dtype, p, a->n_pairs, (hipStream_t)stream);
   DL_CHECK_LAUNCH("dl_pgca_pairs_ragged_fwd");
   return DL_OK;

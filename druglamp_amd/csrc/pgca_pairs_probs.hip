@@ -3,14 +3,13 @@
 // over dense per-entity codes (dl_pgca_pairs_probs) or over a packed per-drug row store (dl_pgca_pairs_ragged_probs: the
 // resident drug library).  See include/druglamp_hip.h for the addressing of both.  No value row is read.
 //
-//   The operands are those of pgca_pairs.hip (cached per-entity codes, nothing gathered per pair), and so is the way a
-//   workgroup finds its keys: the `Keys` types of pair_keys.cuh (DenseKeys / RaggedKeys, one locate()).  What is written is
-//   what attn_probs.hip writes for one (problem, head) — here with every drug's own key count and multiplicity.
+//   The operands, the `Keys` types and the guards are pair_keys.cuh's; what is written is what attn_probs.hip writes for one
+//   (problem, head) — here with every drug's own key count and multiplicity.
 //
 //   pgca_pairs_probs_kernel : one workgroup owns 64 * QT query rows of one pair; a wave owns 16 * QT of them.  It sweeps the
 //                       drug's 64-key tiles TWICE through two LDS buffers by LDS-DMA (one pipeline of 2 * nt tiles):
 //                         sweep 1  scores in the transposed layout (S^T = K Q^T, lane (il, g) holds keys 4g + r of query
-//                                  il), running maximum and sum — attn_lse_kernel's arithmetic; the LSE stays in registers;
+//                                  il), running maximum and sum; the LSE stays in registers;
 //                         sweep 2  the scores again (a drug has at most ~520 distinct keys: the second read comes from L2),
 //                                  exp2(s c - lse2), passed through a per-wave LDS tile so that the stores run along rows
 //                                  (16 bytes per lane where `out` allows it) — attn_probs_kernel's emit, with the tail keys'
@@ -18,12 +17,9 @@
 //                       No workspace, no second launch, no atomics on `out`: two calls agree bitwise.  The columns between
 //                       the drug's own count and out_cols are zero filled by the same workgroup (plain vector stores, under
 //                       the first tile's DMA).  The grid is n_pairs x ceil(Lq / (64 QT)).
-//                       A pair whose index is out of range (DL_FLAG_PAIR_INDEX), whose drug's table entry does not describe
-//                       rows inside the store (DL_FLAG_KEY_TABLE), or whose map does not fit (more columns than out_cols, or
-//                       expand_tail with a multiplicity that is no whole number <= 2^24: DL_FLAG_MAP_COLS) returns before it
-//                       reads anything through the entry or writes anything; all tests are uniform for the workgroup.
+//                       The multiplicity is tested under expand_tail only, and the tail bias is KeySeg's (the host's for dense
+//                       keys); there is no bound on the stored keys.
 #include "pair_keys.cuh"
-#include "tiles.cuh"
 
 namespace {
 using namespace dltile;
@@ -47,11 +43,6 @@ template <typename Keys> struct MapP : MapCommon {
   Keys keys;
 };
 
-// the multiplicity of drug di's tail keys (only read for an entry that locate() accepted)
-__device__ __forceinline__ float tail_weight(const DenseKeys&, int, float dense_w) { return dense_w; }
-__device__ __forceinline__ float tail_weight(const RaggedKeys& k, int di, float) { return k.tailw[di]; }
-
-constexpr int KVB = 64, NKT = KVB / 16;   // keys per streamed tile, 16-key score tiles in it
 constexpr int SP = KVB + 4;               // pitch of the per-wave staging tile in floats (as attn_probs.hip)
 
 // LDS: two K tiles + the staging tiles = 49 KB in bf16 (three workgroups per CU), 81 KB in fp32 (one: the parity dtype)
@@ -67,28 +58,15 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_probs_kernel(const 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, il = lane & 15, g = lane >> 4;
   const int n = blockIdx.x / p.bps, qb = blockIdx.x % p.bps;
   const int pi = p.qi[n], di = p.ki[n];
-  // All guards are uniform for the workgroup: the indices, what locate() reads and the multiplicity are scalar loads (the
-  // keys' entry is read only through an index in range), all of them in front of the one atomic.
   KeySeg ks = {};
-  const bool in_range = (unsigned)pi < (unsigned)p.n_q && (unsigned)di < (unsigned)p.n_kv;
-  uint32_t bad = in_range ? p.keys.locate(di, p.k_rs, 0, p.scale, ks) : (uint32_t)DL_FLAG_PAIR_INDEX;
-  int copies = 1;
-  int64_t cols64 = ks.Lk;                               // columns of this drug's map
-  if (!bad && p.expand && ks.Lk > ks.tail_start) {
-    const float w = tail_weight(p.keys, di, p.dense_w);
-    if (w <= 16777216.f && w == truncf(w)) {
-      copies = (int)w;
-      cols64 = (int64_t)ks.tail_start + (int64_t)(ks.Lk - ks.tail_start) * copies;
-    } else {
-      bad = DL_FLAG_MAP_COLS;
-    }
-  }
-  if (!bad && cols64 > (int64_t)p.out_cols) bad = DL_FLAG_MAP_COLS;
-  if (bad) {                                            // the pair is skipped: nothing read through the entry, nothing written
-    if (p.flags && qb == 0 && threadIdx.x == 0) atomicOr(p.flags, bad);
+  int copies, cols;
+  float unused_bias;
+  const uint32_t bad = map_guard(p, pi, di, p.expand != 0, INT32_MAX, ks, copies, cols, unused_bias);
+  if (bad) {
+    flag_pair(p.flags, bad, qb == 0 && threadIdx.x == 0);
     return;
   }
-  const int Lk = ks.Lk, tail_start = ks.tail_start, tail_rows = Lk - tail_start, cols = (int)cols64;
+  const int Lk = ks.Lk, tail_start = ks.tail_start, tail_rows = Lk - tail_start;
   const float tail_bias = ks.tail_bias;
   const T* Qb = reinterpret_cast<const T*>(p.Q) + (int64_t)pi * p.q_es;
   const T* Kb = reinterpret_cast<const T*>(p.K) + ks.k_off;
@@ -96,12 +74,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_probs_kernel(const 
 
   const int qw0 = qb * QB + wave * QT * 16;
   u32x4 qf[QT][NKF];
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    const int q = qw0 + qt * 16 + il;
-#pragma unroll
-    for (int kf = 0; kf < NKF; ++kf) qf[qt][kf] = frag_global<T>(Qb + (int64_t)q * p.q_rs, q < p.Lq, kf, g);
-  }
+  load_q_frags(qf, Qb, p.q_rs, qw0, p.Lq, il, g);
   const float c = p.scale * LOG2E;
   const int nt = (Lk + KVB - 1) / KVB;
   auto stage = [&](int i) {                             // pipeline step i: tile i % nt into buffer i & 1
@@ -185,14 +158,14 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_probs_kernel(const 
     vm_wait<0>();                                       // this wave's share of step i's LDS-DMA (not implied by the barrier)
     __syncthreads();                                    // the tile has landed; everyone is done with the other buffer
     if (i + 1 < 2 * nt) stage(i + 1);
-    if (i == nt) {                                      // between the sweeps: LSE_q = m scale + log l, as attn_lse_kernel
+    if (i == nt) {                                      // between the sweeps
 #pragma unroll
-      for (int qt = 0; qt < QT; ++qt) lse2[qt] = (m_run[qt] * p.scale + logf(group4_sum(l_run[qt]))) * LOG2E;
+      for (int qt = 0; qt < QT; ++qt) lse2_join(m_run[qt], l_run[qt], p.scale, lse2[qt]);
     }
     f32x4 s[QT][NKT];
     fwd_scores<T, HD>(smem + (i & 1) * BUF, qf, s, il, g);      // S^T = K Q^T
     if (!second) {
-      // ---- sweep 1: key multiplicities, key masking, running maximum and sum ----
+      // ---- sweep 1: key multiplicities, key masking (mask_keys(), kept in place), running maximum and sum ----
       if (k0 + KVB > tail_start || k0 + KVB > Lk) {
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt)
@@ -206,37 +179,10 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_probs_kernel(const 
             }
           }
       }
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[qt][kt][r]);
-        mx = group4_max(mx);
-        const float m_new = fmaxf(m_run[qt], mx);
-        const float alpha = fast_exp2((m_run[qt] - m_new) * c);
-        const float mc = m_new * c;
-        float rs = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) rs += fast_exp2(s[qt][kt][r] * c - mc);
-        l_run[qt] = l_run[qt] * alpha + rs;             // per-lane partial (own keys); reduced between the sweeps
-        m_run[qt] = m_new;
-      }
+      sweep_stats(s, m_run, l_run, c);
     } else {
       // ---- sweep 2: a tail key carries the mass of the keys it stands for, except where each copy gets its own column ----
-      if (!p.expand && k0 + KVB > tail_start) {
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (k0 + kt * 16 + 4 * g + r >= tail_start) {
-#pragma unroll
-              for (int qt = 0; qt < QT; ++qt) s[qt][kt][r] += tail_bias;
-            }
-      }
+      if (!p.expand) bias_tail_keys(s, k0, tail_start, tail_bias, g);
 #pragma unroll
       for (int qt = 0; qt < QT; ++qt) {
 #pragma unroll
@@ -251,51 +197,33 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void pgca_pairs_probs_kernel(const 
   }
 }
 
-template <typename T> constexpr int map_qt() { return sizeof(T) == 2 ? 2 : 1; }
-
 template <typename Keys>
 void launch_maps(int dtype, const MapP<Keys>& p, int n_pairs, hipStream_t s) {
-  const dim3 grid((uint32_t)n_pairs * (uint32_t)p.bps);
-  if (dtype == DL_BF16) hipLaunchKernelGGL((pgca_pairs_probs_kernel<bf16_t, 128, map_qt<bf16_t>(), Keys>), grid, dim3(ATT_THREADS), 0, s, p);
-  else hipLaunchKernelGGL((pgca_pairs_probs_kernel<float, 128, map_qt<float>(), Keys>), grid, dim3(ATT_THREADS), 0, s, p);
+  launch_by_dtype(dtype, pgca_pairs_probs_kernel<bf16_t, 128, pair_qt<bf16_t>(), Keys>, pgca_pairs_probs_kernel<float, 128, pair_qt<float>(), Keys>,
+                  (uint32_t)n_pairs * (uint32_t)p.bps, ATT_THREADS, s, p);
 }
 
 // What dl_pgca_pairs_probs_args and dl_pgca_pairs_ragged_probs_args share (same field names): the checks, and the common block
-// of the launch.  st / stn: the entry point's operand strides and their names.  Nothing behind a pointer is looked at, and with
-// n_pairs == 0 (no launch) no pointer or stride either.
+// of the launch.  st / stn: the entry point's operand strides and their names.
 template <typename Args>
 int maps_common(const char* who, const Args* a, const int64_t* st, const char* const* stn, int n_st, MapCommon& p) {
-  DL_CHECK_ARG(a->dtype == DL_F32 || a->dtype == DL_BF16, DL_ERR_ARG, "%s: bad dtype %d", who, a->dtype);
-  DL_CHECK_ARG(a->head_dim == 128, DL_ERR_UNSUPPORTED, "%s: head_dim %d (one head of 128 only)", who, a->head_dim);
-  DL_CHECK_ARG(a->n_pairs >= 0 && a->n_q >= 0 && a->n_kv >= 0, DL_ERR_SHAPE, "%s: negative count (n_pairs %d, n_q %d, n_kv %d)", who,
-               a->n_pairs, a->n_q, a->n_kv);
-  DL_CHECK_ARG(a->Lq > 0, DL_ERR_SHAPE, "%s: Lq %d must be positive", who, a->Lq);
-  DL_CHECK_ARG(a->scale > 0.f, DL_ERR_ARG, "%s: scale must be positive", who);
+  DL_TRY(pair_head_checks(who, a));
   DL_CHECK_ARG(a->out_cols > 0, DL_ERR_SHAPE, "%s: out_cols %d must be positive", who, a->out_cols);
   DL_CHECK_ARG(a->expand_tail == 0 || a->expand_tail == 1, DL_ERR_ARG, "%s: expand_tail %d is not 0 or 1", who, a->expand_tail);
   if (a->n_pairs == 0) return DL_OK;
   DL_CHECK_ARG(a->Q && a->K && a->out && a->q_index && a->kv_index, DL_ERR_ARG, "%s: null pointer (Q, K, out, q_index, kv_index)", who);
-  const int epc = 16 / (int)dl_dtype_size(a->dtype);
-  for (int i = 0; i < n_st; ++i)
-    DL_CHECK_ARG(st[i] >= 0 && st[i] % epc == 0, DL_ERR_ALIGN, "%s: stride %s (%ld) not a non-negative multiple of %d elements", who,
-                 stn[i], (long)st[i], epc);
+  DL_TRY(pair_stride_checks(who, a->dtype, st, stn, n_st));
   DL_CHECK_ARG((((uintptr_t)a->Q | (uintptr_t)a->K) & 15) == 0, DL_ERR_ALIGN, "%s: Q / K not 16-byte aligned", who);
   DL_CHECK_ARG(((uintptr_t)a->out & 3) == 0, DL_ERR_ALIGN, "%s: out not 4-byte aligned", who);
-  DL_CHECK_ARG((((uintptr_t)a->q_index | (uintptr_t)a->kv_index | (uintptr_t)a->flags) & 3) == 0, DL_ERR_ALIGN,
-               "%s: q_index / kv_index / flags not 4-byte aligned", who);
+  DL_TRY(pair_index_checks(who, a));
   DL_CHECK_ARG(a->out_ps >= 0, DL_ERR_SHAPE, "%s: out_ps %ld is negative", who, (long)a->out_ps);
   DL_CHECK_ARG(a->out_rs >= (int64_t)a->out_cols, DL_ERR_SHAPE, "%s: out_rs %ld below out_cols = %d", who, (long)a->out_rs, a->out_cols);
-  const int qt = a->dtype == DL_BF16 ? map_qt<bf16_t>() : map_qt<float>();
-  const int bps = (a->Lq + 64 * qt - 1) / (64 * qt);
-  DL_CHECK_ARG((int64_t)a->n_pairs * bps <= INT32_MAX, DL_ERR_SHAPE, "%s: too many workgroups (%d pairs x %d)", who, a->n_pairs, bps);
-  p.Q = (const char*)a->Q; p.K = (const char*)a->K; p.out = a->out;
-  p.qi = a->q_index; p.ki = a->kv_index; p.flags = a->flags;
-  p.q_es = a->q_es; p.q_rs = a->q_rs; p.k_rs = a->k_rs; p.out_ps = a->out_ps; p.out_rs = a->out_rs;
-  p.n_q = a->n_q; p.n_kv = a->n_kv; p.Lq = a->Lq; p.bps = bps;
+  DL_TRY(pair_blocks(who, a, p.bps));
+  fill_pair_head(a, p);
+  p.out = a->out; p.out_ps = a->out_ps; p.out_rs = a->out_rs;
   p.out_cols = a->out_cols;
   p.expand = a->expand_tail;
   p.vec = (((uintptr_t)a->out & 15) == 0 && a->out_ps % 4 == 0 && a->out_rs % 4 == 0) ? 1 : 0;
-  p.scale = a->scale;
   p.dense_w = 1.f;
   return DL_OK;
 }
@@ -304,29 +232,14 @@ int maps_common(const char* who, const Args* a, const int64_t* st, const char* c
 
 extern "C" int dl_pgca_pairs_probs(const dl_pgca_pairs_probs_args* a, dl_stream stream) {
   const char* who = "dl_pgca_pairs_probs";
-  DL_CHECK_ARG(a, DL_ERR_ARG, "%s: null argument block", who);
-  DL_CHECK_ARG(a->Lq > 0 && a->Lk > 0, DL_ERR_SHAPE, "%s: Lq %d, Lk %d must be positive", who, a->Lq, a->Lk);
-  DL_CHECK_ARG(a->key_tail_rows >= 0 && a->key_tail_rows <= a->Lk, DL_ERR_ARG, "%s: key_tail_rows %d not in [0, Lk = %d]", who,
-               a->key_tail_rows, a->Lk);
-  DL_CHECK_ARG(a->key_tail_rows == 0 || a->key_tail_weight >= 1.f, DL_ERR_ARG, "%s: key_tail_weight %g below 1", who,
-               (double)a->key_tail_weight);
+  DL_TRY(dense_head_checks(who, a));
   const int64_t st[] = {a->q_es, a->q_rs, a->k_es, a->k_rs};
   const char* stn[] = {"q_es", "q_rs", "k_es", "k_rs"};
   MapP<DenseKeys> p = {};
-  const int rc = maps_common(who, a, st, stn, 4, p);
-  if (rc != DL_OK) return rc;
-  // the column count is launch-wide here: checked on the host (the kernel's DL_FLAG_MAP_COLS guard then never trips)
-  const bool expand = a->expand_tail && a->key_tail_rows > 0;
-  DL_CHECK_ARG(!expand || (a->key_tail_weight <= 16777216.f && a->key_tail_weight == (float)(int64_t)a->key_tail_weight), DL_ERR_ARG,
-               "%s: expand_tail needs a whole key_tail_weight (got %g)", who, (double)a->key_tail_weight);
-  const int64_t cols = expand ? (int64_t)(a->Lk - a->key_tail_rows) + (int64_t)a->key_tail_rows * (int64_t)a->key_tail_weight : (int64_t)a->Lk;
-  DL_CHECK_ARG(cols <= (int64_t)a->out_cols, DL_ERR_SHAPE, "%s: a map of %ld columns does not fit out_cols = %d", who, (long)cols, a->out_cols);
+  DL_TRY(maps_common(who, a, st, stn, 4, p));
+  DL_TRY(dense_cols_check(who, a, a->expand_tail && a->key_tail_rows > 0, "expand_tail needs", "map"));
   if (a->n_pairs == 0) return DL_OK;
-  p.keys.k_es = a->k_es; p.keys.v_es = 0;
-  p.keys.Lk = a->Lk;
-  p.keys.tail_start = a->Lk - a->key_tail_rows;
-  p.keys.tail_bias = a->key_tail_rows ? logf(a->key_tail_weight) / a->scale : 0.f;
-  p.dense_w = a->key_tail_rows ? a->key_tail_weight : 1.f;
+  p.dense_w = fill_dense_keys(a, 0, true, p.keys);
   launch_maps(a->dtype, p, a->n_pairs, (hipStream_t)stream);
   DL_CHECK_LAUNCH("dl_pgca_pairs_probs");
   return DL_OK;
@@ -334,21 +247,13 @@ extern "C" int dl_pgca_pairs_probs(const dl_pgca_pairs_probs_args* a, dl_stream 
 
 extern "C" int dl_pgca_pairs_ragged_probs(const dl_pgca_pairs_ragged_probs_args* a, dl_stream stream) {
   const char* who = "dl_pgca_pairs_ragged_probs";
-  DL_CHECK_ARG(a, DL_ERR_ARG, "%s: null argument block", who);
-  DL_CHECK_ARG(a->kv_total_rows >= 0, DL_ERR_SHAPE, "%s: kv_total_rows %ld is negative", who, (long)a->kv_total_rows);
-  DL_CHECK_ARG(a->key_tail_rows >= 0, DL_ERR_ARG, "%s: key_tail_rows %d is negative", who, a->key_tail_rows);
+  DL_TRY(ragged_head_checks(who, a));
   const int64_t st[] = {a->q_es, a->q_rs, a->k_rs};
   const char* stn[] = {"q_es", "q_rs", "k_rs"};
   MapP<RaggedKeys> p = {};
   const int rc = maps_common(who, a, st, stn, 3, p);
   if (rc != DL_OK || a->n_pairs == 0) return rc;
-  DL_CHECK_ARG(a->kv_row0 && a->kv_keys && a->kv_tail_weight, DL_ERR_ARG, "%s: null pointer (kv_row0, kv_keys, kv_tail_weight)", who);
-  DL_CHECK_ARG(((uintptr_t)a->kv_row0 & 7) == 0, DL_ERR_ALIGN, "%s: kv_row0 not 8-byte aligned", who);
-  DL_CHECK_ARG((((uintptr_t)a->kv_keys | (uintptr_t)a->kv_tail_weight) & 3) == 0, DL_ERR_ALIGN,
-               "%s: kv_keys / kv_tail_weight not 4-byte aligned", who);
-  p.keys.row0 = a->kv_row0; p.keys.keys = a->kv_keys; p.keys.tailw = a->kv_tail_weight;
-  p.keys.total_rows = a->kv_total_rows;
-  p.keys.tail_rows = a->key_tail_rows;
+  DL_TRY(fill_ragged_keys(who, a, p.keys));
   launch_maps(a->dtype, p, a->n_pairs, (hipStream_t)stream);
   DL_CHECK_LAUNCH("dl_pgca_pairs_ragged_probs");
   return DL_OK;

@@ -1,5 +1,6 @@
 // tiles.cuh — LDS tile image + MFMA fragment loaders shared by the attention and NT-Xent kernels, the LDS-DMA row loader
-// of the attention kernels and the three tile steps of the streamed forward.
+// of the attention kernels, the three tile steps of the streamed forward, and the steps of the kernels that take the softmax
+// statistics first: key masking, running statistics, LSE.
 // Tiles are [rows][HD] with 16-byte chunks XOR-swizzled by ATile::swz(row); the same image serves
 // ds_read_b128 (K-contiguous fragments) and ds_read_b64_tr_b16 / ds_read_b32 (transposed fragments).
 #pragma once
@@ -192,6 +193,78 @@ __device__ __forceinline__ void fwd_accumulate(const char* Vs, const f32x4 (&s)[
       for (int qt = 0; qt < QT; ++qt) o[d][qt] = Mma<T>::mma(va, pb[qt], o[d][qt]);
     }
   }
+}
+
+// ---- the tile steps of the kernels that need the softmax statistics first (attn_probs.hip and the two-sweep pair-indexed
+//      kernels), same layout ----
+// key multiplicities and key masking on the tile at key k0: tail keys get the bias on the UNSCALED score, keys >= Lk leave the
+// softmax.  Tiles in front of both skip this through a uniform branch.
+template <int QT, int NKT>
+__device__ __forceinline__ void mask_keys(f32x4 (&s)[QT][NKT], int k0, int Lk, int tail_start, float tail_bias, int g) {
+  if (k0 + NKT * 16 > tail_start || k0 + NKT * 16 > Lk) {
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = k0 + kt * 16 + 4 * g + r;
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) {
+          if (key >= tail_start) s[qt][kt][r] += tail_bias;
+          if (key >= Lk) s[qt][kt][r] = -INFINITY;
+        }
+      }
+  }
+}
+// the tail bias alone, where the statistics are known and no key is masked (a second pass over the scores)
+template <int QT, int NKT>
+__device__ __forceinline__ void bias_tail_keys(f32x4 (&s)[QT][NKT], int k0, int tail_start, float tail_bias, int g) {
+  if (k0 + NKT * 16 > tail_start) {
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (k0 + kt * 16 + 4 * g + r >= tail_start) {
+#pragma unroll
+          for (int qt = 0; qt < QT; ++qt) s[qt][kt][r] += tail_bias;
+        }
+  }
+}
+// running maximum and sum (fwd_softmax's, s left as it is); WITH_G: under the same rescale the running sum of e g, g from a
+// second score array gs (attributions).
+// l_run / d_run are per-lane partials (own keys): lse2_join() reduces them.
+template <bool WITH_G = false, int QT, int NKT>
+__device__ __forceinline__ void sweep_stats(const f32x4 (&s)[QT][NKT], float (&m_run)[QT], float (&l_run)[QT], float c,
+                                            const f32x4 (*gs)[NKT] = nullptr, float* d_run = nullptr) {
+#pragma unroll
+  for (int qt = 0; qt < QT; ++qt) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[qt][kt][r]);
+    mx = group4_max(mx);
+    const float m_new = fmaxf(m_run[qt], mx);
+    const float alpha = fast_exp2((m_run[qt] - m_new) * c);
+    const float mc = m_new * c;
+    float rs = 0.f, rd = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = fast_exp2(s[qt][kt][r] * c - mc);       // w exp(..) on a tail key: the bias is inside
+        rs += e;
+        if constexpr (WITH_G) rd = fmaf(e, gs[qt][kt][r], rd);
+      }
+    l_run[qt] = l_run[qt] * alpha + rs;
+    if constexpr (WITH_G) d_run[qt] = d_run[qt] * alpha + rd;
+    m_run[qt] = m_new;
+  }
+}
+// between the sweeps: a query's sum from its four lanes' partials (returned), lse2 = LSE_q = m scale + log l in exp2 units
+__device__ __forceinline__ float lse2_join(float m_run, float l_run, float scale, float& lse2) {
+  const float l = group4_sum(l_run);
+  lse2 = (m_run * scale + logf(l)) * LOG2E;
+  return l;
 }
 
 // ---- LDS-DMA as inline assembly (invisible to the compiler's wait-count model: counted vmcnt waits stay counted) ----

@@ -475,6 +475,63 @@ def _check_pair_operands(who, q, store, store_name, store_dims, q_index, kv_inde
             raise ValueError("%s: q_index / kv_index must be contiguous int32 vectors of one length" % who)
 
 
+def _fill_pair_head(a, q, store, q_index, kv_index, scale):
+    """The fields that all eight pair-indexed argument blocks share (after _check_pair_operands)."""
+    a.Q, a.K = q.data_ptr(), store.data_ptr()
+    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
+    a.q_es, a.q_rs = q.stride(0), q.stride(1)
+    a.k_rs = store.stride(-2)
+    a.n_pairs, (a.n_q, a.Lq, a.head_dim), a.dtype = q_index.numel(), q.shape, _dt(q)
+    a.scale = float(scale)
+
+
+def _check_cols(who, cols):
+    cols = int(cols)
+    if cols < 1:
+        raise ValueError("%s: cols %d must be positive" % (who, cols))
+    return cols
+
+
+def _dense_keys(a, kv, key_tail, cols=0, expand=False):
+    """The dense-key fields of an argument block: key_tail = (rows, weight), and from kv (n_kv, Lk, 256) the entity stride and
+    counts.  Returns cols, by default the columns of a map: Lk, or under `expand` the full key count Lk - rows + rows * weight
+    (0 where kv has no such shape: the operand checks that follow reject it)."""
+    t, w = (int(key_tail[0]), float(key_tail[1])) if key_tail is not None else (0, 1.0)
+    if key_tail is not None:
+        a.key_tail_rows, a.key_tail_weight = t, w
+    if kv.dim() == 3:
+        a.k_es = kv.stride(0)
+        a.n_kv, a.Lk = kv.shape[:2]
+        if cols is None:
+            cols = kv.shape[1] - t + t * int(w) if (expand and t) else kv.shape[1]
+    return cols or 0
+
+
+def _check_key_table(who, q, row0, n_keys, tail_weight, key_tail_rows=0):
+    for t, dt, what in ((row0, torch.int64, "row0 int64"), (n_keys, torch.int32, "n_keys int32"), (tail_weight, torch.float32, "tail_weight float32")):
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() != row0.numel() or t.device != q.device:
+            raise ValueError("%s: the key table is three contiguous vectors of one length on q's device "
+                             "(row0 int64, n_keys int32, tail_weight float32); %s is %s %s" % (who, what, t.dtype, tuple(t.shape)))
+    if int(key_tail_rows) < 0:
+        raise ValueError("%s: key_tail_rows %d is negative" % (who, int(key_tail_rows)))
+
+
+def _fill_key_table(a, rows, row0, n_keys, tail_weight, key_tail_rows):
+    """The ragged-key fields of an argument block (after _check_key_table and _check_pair_operands)."""
+    a.kv_row0, a.kv_keys, a.kv_tail_weight = row0.data_ptr(), n_keys.data_ptr(), tail_weight.data_ptr()
+    a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
+    a.key_tail_rows = int(key_tail_rows)
+
+
+def _rows_out_ok(out, specs, n_pairs, device):
+    """out is one 2-D tensor per (dtype, width) of specs: (n_pairs, >= width) on device, contiguous columns, non-overlapping rows."""
+    ok = isinstance(out, (tuple, list)) and len(out) == len(specs)
+    for t, (dt, width) in zip(out if ok else (), specs):
+        ok = ok and (t.dim() == 2 and t.dtype == dt and t.device == device and t.shape[0] == n_pairs and t.shape[1] >= width
+                     and t.stride(1) == 1 and t.stride(0) >= width)
+    return ok
+
+
 def _pgca_pairs_common(who, a, q, store, store_name, store_dims, q_index, kv_index, scale, left, bias, out):
     """What pgca_pairs and pgca_pairs_ragged share: the checks of q, of the [K | V'] store (store_name and the names of its
     leading dimensions are what the messages call it), of the index vectors, left and bias; out, allocated or validated; the
@@ -495,16 +552,13 @@ def _pgca_pairs_common(who, a, q, store, store_name, store_dims, q_index, kv_ind
           or out.shape[2] < cols or out.stride(2) != 1 or out.stride(1) < cols or (n_pairs > 1 and out.stride(0) < (Lq - 1) * out.stride(1) + cols)):
         raise ValueError("%s: out must be a %s tensor of (%d, %d, >= %d) on q's device with contiguous columns and "
                          "non-overlapping rows (got %s, strides %s)" % (who, q.dtype, n_pairs, Lq, cols, tuple(out.shape), out.stride()))
-    a.Q, a.K, a.V, a.left, a.out, a.bias = q.data_ptr(), store.data_ptr(), store.data_ptr() + E * store.element_size(), _ptr(left), out.data_ptr(), _ptr(bias)
-    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
-    a.q_es, a.q_rs = q.stride(0), q.stride(1)
-    a.k_rs = a.v_rs = store.stride(-2)
+    _fill_pair_head(a, q, store, q_index, kv_index, scale)
+    a.V, a.left, a.out, a.bias = store.data_ptr() + E * store.element_size(), _ptr(left), out.data_ptr(), _ptr(bias)
+    a.v_rs = a.k_rs
     if left is not None:
         a.left_es, a.left_rs = left.stride(0), left.stride(1)
     a.out_ps, a.out_rs = out.stride(0), out.stride(1)
-    a.n_pairs, a.n_q, a.Lq, a.head_dim, a.dtype = n_pairs, n_q, Lq, E, _dt(q)
     a.left_cols, a.out_col0 = left_cols, left_cols
-    a.scale = float(scale)
     return out
 
 
@@ -518,11 +572,9 @@ def pgca_pairs(q, kv, q_index, kv_index, *, scale, left=None, bias=None, key_tai
     with an index out of range is skipped and sets FLAG_PAIR_INDEX in the device guard word (check_guard_flags)."""
     _need_gpu(q, kv, q_index, kv_index, left, bias, out)
     a = PgcaPairsArgs()
+    _dense_keys(a, kv, key_tail)
+    a.v_es = a.k_es
     out = _pgca_pairs_common("pgca_pairs", a, q, kv, "kv", ("n_kv", "Lk"), q_index, kv_index, scale, left, bias, out)
-    a.k_es = a.v_es = kv.stride(0)
-    a.n_kv, a.Lk = kv.shape[:2]
-    if key_tail is not None:
-        a.key_tail_rows, a.key_tail_weight = int(key_tail[0]), float(key_tail[1])
     check(_lib.lib().dl_pgca_pairs_fwd(C.byref(a), _stream()), "dl_pgca_pairs_fwd")
     return out
 
@@ -535,47 +587,29 @@ def pgca_pairs_ragged(q, rows, row0, n_keys, tail_weight, q_index, kv_index, *, 
     A pair with an index out of range sets FLAG_PAIR_INDEX, one whose drug's table entry does not describe rows inside
     `rows` sets FLAG_KEY_TABLE in the device guard word (check_guard_flags); either pair is skipped."""
     _need_gpu(q, rows, row0, n_keys, tail_weight, q_index, kv_index, left, bias, out)
-    _check_key_table("pgca_pairs_ragged", q, row0, n_keys, tail_weight)
-    if int(key_tail_rows) < 0:
-        raise ValueError("pgca_pairs_ragged: key_tail_rows %d is negative" % int(key_tail_rows))
+    _check_key_table("pgca_pairs_ragged", q, row0, n_keys, tail_weight, key_tail_rows)
     a = PgcaPairsRaggedArgs()
     out = _pgca_pairs_common("pgca_pairs_ragged", a, q, rows, "rows", ("R",), q_index, kv_index, scale, left, bias, out)
-    a.kv_row0, a.kv_keys, a.kv_tail_weight = row0.data_ptr(), n_keys.data_ptr(), tail_weight.data_ptr()
-    a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
-    a.key_tail_rows = int(key_tail_rows)
+    _fill_key_table(a, rows, row0, n_keys, tail_weight, key_tail_rows)
     check(_lib.lib().dl_pgca_pairs_ragged_fwd(C.byref(a), _stream()), "dl_pgca_pairs_ragged_fwd")
     return out
-
-
-def _check_key_table(who, q, row0, n_keys, tail_weight):
-    for t, dt, what in ((row0, torch.int64, "row0 int64"), (n_keys, torch.int32, "n_keys int32"), (tail_weight, torch.float32, "tail_weight float32")):
-        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() != row0.numel() or t.device != q.device:
-            raise ValueError("%s: the key table is three contiguous vectors of one length on q's device "
-                             "(row0 int64, n_keys int32, tail_weight float32); %s is %s %s" % (who, what, t.dtype, tuple(t.shape)))
 
 
 def _pgca_maps_common(who, a, q, store, store_name, store_dims, q_index, kv_index, scale, cols, expand_tail, out):
     """What pgca_pairs_probs and pgca_pairs_ragged_probs share: the checks of q, of the [K | V'] store and of the index vectors;
     out (n_pairs, Lq, cols) fp32, allocated or validated; the fields the two argument blocks have in common.  Returns out."""
     _check_pair_operands(who, q, store, store_name, store_dims, q_index, kv_index)
-    cols = int(cols)
-    if cols < 1:
-        raise ValueError("%s: cols %d must be positive" % (who, cols))
-    n_pairs, (n_q, Lq, E) = q_index.numel(), q.shape
+    cols = _check_cols(who, cols)
+    n_pairs, Lq = q_index.numel(), q.shape[1]
     if out is None:
         out = torch.empty((n_pairs, Lq, cols), dtype=torch.float32, device=q.device)
     elif (out.dim() != 3 or out.dtype != torch.float32 or out.device != q.device or out.shape[0] != n_pairs or out.shape[1] != Lq
           or out.shape[2] < cols or out.stride(2) != 1 or out.stride(1) < cols or (n_pairs > 1 and out.stride(0) < (Lq - 1) * out.stride(1) + cols)):
         raise ValueError("%s: out must be a float32 tensor of (%d, %d, >= %d) on q's device with contiguous columns and "
                          "non-overlapping rows (got %s %s, strides %s)" % (who, n_pairs, Lq, cols, out.dtype, tuple(out.shape), out.stride()))
-    a.Q, a.K, a.out = q.data_ptr(), store.data_ptr(), out.data_ptr()
-    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
-    a.q_es, a.q_rs = q.stride(0), q.stride(1)
-    a.k_rs = store.stride(-2)
-    a.out_ps, a.out_rs = out.stride(0), out.stride(1)
-    a.n_pairs, a.n_q, a.Lq, a.head_dim, a.dtype = n_pairs, n_q, Lq, E, _dt(q)
+    _fill_pair_head(a, q, store, q_index, kv_index, scale)
+    a.out, a.out_ps, a.out_rs = out.data_ptr(), out.stride(0), out.stride(1)
     a.out_cols, a.expand_tail = cols, int(bool(expand_tail))
-    a.scale = float(scale)
     return out
 
 
@@ -589,14 +623,8 @@ def pgca_pairs_probs(q, kv, q_index, kv_index, *, scale, key_tail=None, expand_t
     an index out of range is skipped and sets FLAG_PAIR_INDEX in the device guard word (check_guard_flags)."""
     _need_gpu(q, kv, q_index, kv_index, out)
     a = PgcaPairsProbsArgs()
-    t, w = (int(key_tail[0]), float(key_tail[1])) if key_tail is not None else (0, 1.0)
-    if cols is None and kv.dim() == 3:
-        cols = kv.shape[1] - t + t * int(w) if (expand_tail and t) else kv.shape[1]
-    out = _pgca_maps_common("pgca_pairs_probs", a, q, kv, "kv", ("n_kv", "Lk"), q_index, kv_index, scale, cols or 0, expand_tail, out)
-    a.k_es = kv.stride(0)
-    a.n_kv, a.Lk = kv.shape[:2]
-    if key_tail is not None:
-        a.key_tail_rows, a.key_tail_weight = t, w
+    cols = _dense_keys(a, kv, key_tail, cols, expand_tail)
+    out = _pgca_maps_common("pgca_pairs_probs", a, q, kv, "kv", ("n_kv", "Lk"), q_index, kv_index, scale, cols, expand_tail, out)
     check(_lib.lib().dl_pgca_pairs_probs(C.byref(a), _stream()), "dl_pgca_pairs_probs")
     return out
 
@@ -609,14 +637,10 @@ def pgca_pairs_ragged_probs(q, rows, row0, n_keys, tail_weight, q_index, kv_inde
     its drug's table entry does not describe rows inside `rows` (FLAG_KEY_TABLE), or its map has more than `cols` columns or
     expand_tail meets a weight that is not whole (FLAG_MAP_COLS)."""
     _need_gpu(q, rows, row0, n_keys, tail_weight, q_index, kv_index, out)
-    _check_key_table("pgca_pairs_ragged_probs", q, row0, n_keys, tail_weight)
-    if int(key_tail_rows) < 0:
-        raise ValueError("pgca_pairs_ragged_probs: key_tail_rows %d is negative" % int(key_tail_rows))
+    _check_key_table("pgca_pairs_ragged_probs", q, row0, n_keys, tail_weight, key_tail_rows)
     a = PgcaPairsRaggedProbsArgs()
     out = _pgca_maps_common("pgca_pairs_ragged_probs", a, q, rows, "rows", ("R",), q_index, kv_index, scale, cols, expand_tail, out)
-    a.kv_row0, a.kv_keys, a.kv_tail_weight = row0.data_ptr(), n_keys.data_ptr(), tail_weight.data_ptr()
-    a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
-    a.key_tail_rows = int(key_tail_rows)
+    _fill_key_table(a, rows, row0, n_keys, tail_weight, key_tail_rows)
     check(_lib.lib().dl_pgca_pairs_ragged_probs(C.byref(a), _stream()), "dl_pgca_pairs_ragged_probs")
     return out
 
@@ -626,33 +650,24 @@ def _pgca_profile_common(who, a, q, store, store_name, store_dims, q_index, kv_i
     vectors; the outputs (key_mass (n_pairs, cols) fp32, site_peak (n_pairs, Lq) fp32, site_key (n_pairs, Lq) int32), allocated
     or validated; the fields the two argument blocks have in common.  Returns the three outputs."""
     _check_pair_operands(who, q, store, store_name, store_dims, q_index, kv_index)
-    cols = int(cols)
-    if cols < 1:
-        raise ValueError("%s: cols %d must be positive" % (who, cols))
-    n_pairs, (n_q, Lq, E) = q_index.numel(), q.shape
+    cols = _check_cols(who, cols)
+    n_pairs, Lq = q_index.numel(), q.shape[1]
     if out is None:
         out = (torch.empty((n_pairs, cols), dtype=torch.float32, device=q.device),
                torch.empty((n_pairs, Lq), dtype=torch.float32, device=q.device),
                torch.empty((n_pairs, Lq), dtype=torch.int32, device=q.device))
     else:
-        ok = isinstance(out, (tuple, list)) and len(out) == 3
-        for t, dt, width in zip(out if ok else (), (torch.float32, torch.float32, torch.int32), (cols, Lq, Lq)):
-            ok = ok and (t.dim() == 2 and t.dtype == dt and t.device == q.device and t.shape[0] == n_pairs and t.shape[1] >= width
-                         and t.stride(1) == 1 and t.stride(0) >= width)
+        ok = _rows_out_ok(out, ((torch.float32, cols), (torch.float32, Lq), (torch.int32, Lq)), n_pairs, q.device)
         if not ok or out[1].stride(0) != out[2].stride(0):
             raise ValueError("%s: out must be (key_mass float32 (%d, >= %d), site_peak float32 (%d, >= %d), site_key int32 (%d, >= %d)) "
                              "on q's device with contiguous columns, non-overlapping rows and one row pitch for the two site "
                              "outputs" % (who, n_pairs, cols, n_pairs, Lq, n_pairs, Lq))
         out = tuple(out)
     mass, peak, skey = out
-    a.Q, a.K, a.key_mass, a.site_peak, a.site_key = q.data_ptr(), store.data_ptr(), mass.data_ptr(), peak.data_ptr(), skey.data_ptr()
-    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
-    a.q_es, a.q_rs = q.stride(0), q.stride(1)
-    a.k_rs = store.stride(-2)
+    _fill_pair_head(a, q, store, q_index, kv_index, scale)
+    a.key_mass, a.site_peak, a.site_key = mass.data_ptr(), peak.data_ptr(), skey.data_ptr()
     a.mass_ps, a.site_ps = mass.stride(0), peak.stride(0)
-    a.n_pairs, a.n_q, a.Lq, a.head_dim, a.dtype = n_pairs, n_q, Lq, E, _dt(q)
     a.out_cols = cols
-    a.scale = float(scale)
     return out
 
 
@@ -667,14 +682,8 @@ def pgca_pairs_profile(q, kv, q_index, kv_index, *, scale, key_tail=None, cols=N
     pitch).  A pair with an index out of range is skipped and sets FLAG_PAIR_INDEX in the device guard word."""
     _need_gpu(q, kv, q_index, kv_index, *(out if isinstance(out, (tuple, list)) else ()))
     a = PgcaPairsProfileArgs()
-    t, w = (int(key_tail[0]), float(key_tail[1])) if key_tail is not None else (0, 1.0)
-    if cols is None and kv.dim() == 3:
-        cols = kv.shape[1] - t + t * int(w) if t else kv.shape[1]
-    out = _pgca_profile_common("pgca_pairs_profile", a, q, kv, "kv", ("n_kv", "Lk"), q_index, kv_index, scale, cols or 0, out)
-    a.k_es = kv.stride(0)
-    a.n_kv, a.Lk = kv.shape[:2]
-    if key_tail is not None:
-        a.key_tail_rows, a.key_tail_weight = t, w
+    cols = _dense_keys(a, kv, key_tail, cols, True)
+    out = _pgca_profile_common("pgca_pairs_profile", a, q, kv, "kv", ("n_kv", "Lk"), q_index, kv_index, scale, cols, out)
     check(_lib.lib().dl_pgca_pairs_profile(C.byref(a), _stream()), "dl_pgca_pairs_profile")
     return out
 
@@ -687,14 +696,10 @@ def pgca_pairs_ragged_profile(q, rows, row0, n_keys, tail_weight, q_index, kv_in
     describe rows inside `rows` (FLAG_KEY_TABLE), or its map has more than `cols` columns, its weight is not whole or it has
     more than 576 stored keys (FLAG_MAP_COLS)."""
     _need_gpu(q, rows, row0, n_keys, tail_weight, q_index, kv_index, *(out if isinstance(out, (tuple, list)) else ()))
-    _check_key_table("pgca_pairs_ragged_profile", q, row0, n_keys, tail_weight)
-    if int(key_tail_rows) < 0:
-        raise ValueError("pgca_pairs_ragged_profile: key_tail_rows %d is negative" % int(key_tail_rows))
+    _check_key_table("pgca_pairs_ragged_profile", q, row0, n_keys, tail_weight, key_tail_rows)
     a = PgcaPairsRaggedProfileArgs()
     out = _pgca_profile_common("pgca_pairs_ragged_profile", a, q, rows, "rows", ("R",), q_index, kv_index, scale, cols, out)
-    a.kv_row0, a.kv_keys, a.kv_tail_weight = row0.data_ptr(), n_keys.data_ptr(), tail_weight.data_ptr()
-    a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
-    a.key_tail_rows = int(key_tail_rows)
+    _fill_key_table(a, rows, row0, n_keys, tail_weight, key_tail_rows)
     check(_lib.lib().dl_pgca_pairs_ragged_profile(C.byref(a), _stream()), "dl_pgca_pairs_ragged_profile")
     return out
 
@@ -704,10 +709,8 @@ def _pgca_attr_common(who, a, q, store, store_name, store_dims, d_out, q_index, 
     d_out and of sites / d_sites; the outputs (key_attr (n_pairs, cols) fp32, site_attr (n_pairs, Lq) fp32), allocated or
     validated; the fields the two argument blocks have in common.  Returns the two outputs."""
     _check_pair_operands(who, q, store, store_name, store_dims, q_index, kv_index)
-    cols = int(cols)
-    if cols < 1:
-        raise ValueError("%s: cols %d must be positive" % (who, cols))
-    n_pairs, (n_q, Lq, E) = q_index.numel(), q.shape
+    cols = _check_cols(who, cols)
+    n_pairs, (Lq, E) = q_index.numel(), q.shape[1:]
     if d_out.dtype != q.dtype:
         raise ValueError("%s: q is %s, d_out is %s" % (who, q.dtype, d_out.dtype))
     if d_out.dim() != 3 or tuple(d_out.shape) != (n_pairs, Lq, E) or d_out.stride(2) != 1:
@@ -725,29 +728,21 @@ def _pgca_attr_common(who, a, q, store, store_name, store_dims, d_out, q_index, 
         out = (torch.empty((n_pairs, cols), dtype=torch.float32, device=q.device),
                torch.empty((n_pairs, Lq), dtype=torch.float32, device=q.device))
     else:
-        ok = isinstance(out, (tuple, list)) and len(out) == 2
-        for t, width in zip(out if ok else (), (cols, Lq)):
-            ok = ok and (t.dim() == 2 and t.dtype == torch.float32 and t.device == q.device and t.shape[0] == n_pairs
-                         and t.shape[1] >= width and t.stride(1) == 1 and t.stride(0) >= width)
-        if not ok:
+        if not _rows_out_ok(out, ((torch.float32, cols), (torch.float32, Lq)), n_pairs, q.device):
             raise ValueError("%s: out must be (key_attr float32 (%d, >= %d), site_attr float32 (%d, >= %d)) on q's device with "
                              "contiguous columns and non-overlapping rows" % (who, n_pairs, cols, n_pairs, Lq))
         out = tuple(out)
     kattr, sattr = out
-    a.Q, a.K, a.dO, a.sites, a.d_sites = q.data_ptr(), store.data_ptr(), d_out.data_ptr(), _ptr(sites), _ptr(d_sites)
+    _fill_pair_head(a, q, store, q_index, kv_index, scale)
+    a.dO, a.sites, a.d_sites = d_out.data_ptr(), _ptr(sites), _ptr(d_sites)
     a.key_attr, a.site_attr = kattr.data_ptr(), sattr.data_ptr()
-    a.q_index, a.kv_index, a.flags = q_index.data_ptr(), kv_index.data_ptr(), guard_flags(q.device).data_ptr()
-    a.q_es, a.q_rs = q.stride(0), q.stride(1)
-    a.k_rs = store.stride(-2)
     a.do_ps, a.do_rs = d_out.stride(0), d_out.stride(1)
     if sites is not None:
         a.left_es, a.left_rs = sites.stride(0), sites.stride(1)
         a.dl_ps, a.dl_rs = d_sites.stride(0), d_sites.stride(1)
         a.left_cols = sites.shape[2]
     a.mass_ps, a.site_ps = kattr.stride(0), sattr.stride(0)
-    a.n_pairs, a.n_q, a.Lq, a.head_dim, a.dtype = n_pairs, n_q, Lq, E, _dt(q)
     a.out_cols = cols
-    a.scale = float(scale)
     return out
 
 
@@ -763,14 +758,8 @@ def pgca_pairs_attr(q, kv, d_out, q_index, kv_index, *, scale, key_tail=None, co
     tensors to write into (rows may be wider)."""
     _need_gpu(q, kv, d_out, q_index, kv_index, sites, d_sites, *(out if isinstance(out, (tuple, list)) else ()))
     a = PgcaPairsAttrArgs()
-    t, w = (int(key_tail[0]), float(key_tail[1])) if key_tail is not None else (0, 1.0)
-    if cols is None and kv.dim() == 3:
-        cols = kv.shape[1] - t + t * int(w) if t else kv.shape[1]
-    out = _pgca_attr_common("pgca_pairs_attr", a, q, kv, "kv", ("n_kv", "Lk"), d_out, q_index, kv_index, scale, cols or 0, sites, d_sites, out)
-    a.k_es = kv.stride(0)
-    a.n_kv, a.Lk = kv.shape[:2]
-    if key_tail is not None:
-        a.key_tail_rows, a.key_tail_weight = t, w
+    cols = _dense_keys(a, kv, key_tail, cols, True)
+    out = _pgca_attr_common("pgca_pairs_attr", a, q, kv, "kv", ("n_kv", "Lk"), d_out, q_index, kv_index, scale, cols, sites, d_sites, out)
     check(_lib.lib().dl_pgca_pairs_attr(C.byref(a), _stream()), "dl_pgca_pairs_attr")
     return out
 
@@ -783,14 +772,10 @@ def pgca_pairs_ragged_attr(q, rows, row0, n_keys, tail_weight, d_out, q_index, k
     A pair is skipped — neither output is written for it — and flagged in the device guard word (check_guard_flags) under
     pgca_pairs_ragged_profile's conditions."""
     _need_gpu(q, rows, row0, n_keys, tail_weight, d_out, q_index, kv_index, sites, d_sites, *(out if isinstance(out, (tuple, list)) else ()))
-    _check_key_table("pgca_pairs_ragged_attr", q, row0, n_keys, tail_weight)
-    if int(key_tail_rows) < 0:
-        raise ValueError("pgca_pairs_ragged_attr: key_tail_rows %d is negative" % int(key_tail_rows))
+    _check_key_table("pgca_pairs_ragged_attr", q, row0, n_keys, tail_weight, key_tail_rows)
     a = PgcaPairsRaggedAttrArgs()
     out = _pgca_attr_common("pgca_pairs_ragged_attr", a, q, rows, "rows", ("R",), d_out, q_index, kv_index, scale, cols, sites, d_sites, out)
-    a.kv_row0, a.kv_keys, a.kv_tail_weight = row0.data_ptr(), n_keys.data_ptr(), tail_weight.data_ptr()
-    a.kv_total_rows, a.n_kv = rows.shape[0], row0.numel()
-    a.key_tail_rows = int(key_tail_rows)
+    _fill_key_table(a, rows, row0, n_keys, tail_weight, key_tail_rows)
     check(_lib.lib().dl_pgca_pairs_ragged_attr(C.byref(a), _stream()), "dl_pgca_pairs_ragged_attr")
     return out
 
