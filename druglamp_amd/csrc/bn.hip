@@ -1,31 +1,8 @@
 // bn.hip — channel-last BatchNorm pieces for the ProteinCNN path (HBM-bound column statistics +
 // elementwise apply), with a row-validity window so that zero-padding halos stay zero.
-#include "common.cuh"
+#include "bn_rows.cuh"
 
 namespace {
-static inline int bn_rows_per_block(int64_t R, int64_t C) {
-  const int64_t colgroups = (C + 255) / 256;
-  int64_t chunks = (1024 + colgroups - 1) / colgroups;
-  int64_t rows = (R + chunks - 1) / chunks;
-  if (rows < 32) rows = 32;
-  return (int)((rows + 3) / 4 * 4);
-}
-
-// 32-bit on purpose: a 64-bit modulo costs ~100 instructions and this runs once per row per thread (R < 2^31 is checked)
-__device__ __forceinline__ bool row_valid(int64_t r, int64_t win, int64_t halo, int64_t valid) {
-  if (win == 0) return true;
-  const uint32_t q = (uint32_t)r % (uint32_t)win;
-  return q >= (uint32_t)halo && q < (uint32_t)(halo + valid);
-}
-
-// Row rule of every kernel below: rw == nullptr -> the window rule above (weight 1 for valid rows); else rw[r] is the row's
-// weight: < 0 halo row (excluded, written as zeros), 0 context row (computed, not part of the statistics), m >= 1 a row that
-// stands for m identical rows (the ProteinCNN compact layout, druglamp_amd/protein_plan.py).  -1 = excluded.
-__device__ __forceinline__ float row_weight(const float* __restrict__ rw, int64_t r, int64_t win, int64_t halo, int64_t valid) {
-  if (rw) return rw[r];
-  return row_valid(r, win, halo, valid) ? 1.f : -1.f;
-}
-
 // grid (ceil(C/256), chunks); lane -> 4 columns; MODE 0: (w y, w y^2); MODE 1: (dz, dz*yhat) over the rows with w >= 0
 // prelu_g / prelu_b (MODE 1 only, round 5): gamma / beta of a BatchNorm whose output went through a ReLU (Linear -> BN -> ReLU of
 // the SimSiam MLPs): the incoming gradient counts only where z = (y - mean) rstd gamma + beta > 0.
@@ -46,7 +23,7 @@ __global__ void bn_partial_kernel(const T* __restrict__ a, const T* __restrict__
     const bool prelu = MODE == 1 && prelu_g != nullptr;
     if (prelu) { pg = *reinterpret_cast<const f32x4*>(prelu_g + c); pb = *reinterpret_cast<const f32x4*>(prelu_b + c); }
     for (int64_t r = r0 + wave; r < r1; r += 4) {
-      const float wr = row_weight(rw, r, win, halo, valid);
+      const float wr = bn_row_weight(rw, r, win, halo, valid);
       if (MODE == 0 ? wr <= 0.f : wr < 0.f) continue;
       f32x4 v = load4<T>(a + r * C + c);
       if (MODE == 0) { const f32x4 t = v * wr; s0 += t; s1 += t * v; }      // (wr = 1: the plain sums, bit for bit)
@@ -61,15 +38,7 @@ __global__ void bn_partial_kernel(const T* __restrict__ a, const T* __restrict__
       }
     }
   }
-  red[0][wave][lane] = s0; red[1][wave][lane] = s1;
-  __syncthreads();
-  if (wave == 0 && c < C) {
-    s0 = red[0][0][lane] + red[0][1][lane] + red[0][2][lane] + red[0][3][lane];
-    s1 = red[1][0][lane] + red[1][1][lane] + red[1][2][lane] + red[1][3][lane];
-    float* d0 = partial + ((int64_t)blockIdx.y * 2 + 0) * C + c;
-    float* d1 = partial + ((int64_t)blockIdx.y * 2 + 1) * C + c;
-    *reinterpret_cast<f32x4*>(d0) = s0; *reinterpret_cast<f32x4*>(d1) = s1;
-  }
+  bn_store_partials(red, s0, s1, lane, wave, c, C, partial);
 }
 
 // bf16, C in {64, 128, 256}: 16-byte loads, every lane busy (256 / (C/8) rows per pass), four passes in flight.
@@ -88,10 +57,6 @@ __global__ __launch_bounds__(256) void bn_partial_wide_kernel(const bf16_t* __re
   float s0[8], s1[8], mu[8], rs[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { s0[e] = 0.f; s1[e] = 0.f; mu[e] = MODE == 1 ? mean[c + e] : 0.f; rs[e] = MODE == 1 ? rstd[c + e] : 1.f; }
-  auto unpack = [](u32x4 w, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { f[2 * i] = bf16lo(w[i]); f[2 * i + 1] = bf16hi(w[i]); }
-  };
   for (int64_t r = r0 + rsub; r < r1; r += 4 * rpp) {
     u32x4 va[4], vy[4];
     bool ok[4];
@@ -99,7 +64,7 @@ __global__ __launch_bounds__(256) void bn_partial_wide_kernel(const bf16_t* __re
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int64_t rr = r + (int64_t)u * rpp;
-      wr[u] = rr < r1 ? row_weight(rw, rr, win, halo, valid) : -1.f;
+      wr[u] = rr < r1 ? bn_row_weight(rw, rr, win, halo, valid) : -1.f;
       ok[u] = MODE == 0 ? wr[u] > 0.f : wr[u] >= 0.f;
       va[u] = u32x4{0u, 0u, 0u, 0u}; vy[u] = va[u];
       if (ok[u]) {
@@ -111,8 +76,8 @@ __global__ __launch_bounds__(256) void bn_partial_wide_kernel(const bf16_t* __re
     for (int u = 0; u < 4; ++u) {
       if (!ok[u]) continue;
       float v[8], w[8];
-      unpack(va[u], v);
-      if (MODE == 1) unpack(vy[u], w);
+      unpack8(va[u], v);
+      if (MODE == 1) unpack8(vy[u], w);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         if (MODE == 0) { const float t = v[e] * wr[u]; s0[e] += t; s1[e] += t * v[e]; }     // (wr = 1: the plain sums, bit for bit)
@@ -120,16 +85,7 @@ __global__ __launch_bounds__(256) void bn_partial_wide_kernel(const bf16_t* __re
       }
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { red[0][tid][e] = s0[e]; red[1][tid][e] = s1[e]; }
-  __syncthreads();
-  // thread t < 2*C sums column (t % C) of array (t / C) over the rpp row groups
-  for (int t = tid; t < 2 * C; t += 256) {
-    const int which = t / C, col = t % C, cch = col >> 3, e = col & 7;
-    float acc = 0.f;
-    for (int g = 0; g < rpp; ++g) acc += red[which][g * cpr + cch][e];
-    partial[((int64_t)blockIdx.y * 2 + which) * C + col] = acc;
-  }
+  bn_store_partials_wide(red, s0, s1, C, partial);
 }
 
 template <typename T, bool RELU = false>
@@ -143,7 +99,7 @@ __global__ void bn_apply_fwd_kernel(const T* __restrict__ y, T* __restrict__ z, 
   const int64_t r = i / c4;
   const int c = (int)(i - (uint32_t)r * c4) * 4;
   f32x4 o = {0.f, 0.f, 0.f, 0.f};
-  if (row_weight(rw, r, win, halo, valid) >= 0.f) {
+  if (bn_row_weight(rw, r, win, halo, valid) >= 0.f) {
     const f32x4 v = load4<T>(y + r * C + c);
     const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c), rs = *reinterpret_cast<const f32x4*>(rstd + c);
     const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c), b = *reinterpret_cast<const f32x4*>(beta + c);
@@ -168,7 +124,7 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ dz, const T* __restric
   const int64_t r = i / c4;
   const int c = (int)(i - (uint32_t)r * c4) * 4;
   f32x4 o = {0.f, 0.f, 0.f, 0.f};
-  const float wr = row_weight(rw, r, win, halo, valid);
+  const float wr = bn_row_weight(rw, r, win, halo, valid);
   if (wr >= 0.f) {
     f32x4 d = load4<T>(dz + r * C + c);
     const f32x4 yv = load4<T>(y + r * C + c);
@@ -198,13 +154,6 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ dz, const T* __restric
 // flight per iteration.  The one-quad-per-thread forms above spend more instructions on index arithmetic and the halo
 // test (a 32-bit modulo per 8 bytes) than on the data: 3.2 / 4.0 TB/s; these: see tools/ln_bench.py.
 constexpr int BN_WIDE_U = 4;
-__device__ __forceinline__ void unpack8(u32x4 w, float (&f)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { f[2 * i] = bf16lo(w[i]); f[2 * i + 1] = bf16hi(w[i]); }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-  return u32x4{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
-}
 
 template <int C>
 __global__ __launch_bounds__(256) void bn_apply_fwd_wide_kernel(const bf16_t* __restrict__ y, bf16_t* __restrict__ z,
@@ -223,7 +172,7 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_wide_kernel(const bf16_t* __
 #pragma unroll
     for (int u = 0; u < BN_WIDE_U; ++u) {
       const int r = r0 + u * stride;
-      ok[u] = r < R && row_weight(rw, r, win, halo, valid) >= 0.f;
+      ok[u] = r < R && bn_row_weight(rw, r, win, halo, valid) >= 0.f;
       w[u] = u32x4{0u, 0u, 0u, 0u};
       if (ok[u]) w[u] = *reinterpret_cast<const u32x4*>(y + (int64_t)r * C + c);
     }
@@ -267,7 +216,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_wide_kernel(const bf16_t* __
 #pragma unroll
     for (int u = 0; u < BN_WIDE_U; ++u) {
       const int r = r0 + u * stride;
-      wr[u] = r < R ? row_weight(rw, r, win, halo, valid) : -1.f;
+      wr[u] = r < R ? bn_row_weight(rw, r, win, halo, valid) : -1.f;
       ok[u] = wr[u] >= 0.f;
       wd[u] = u32x4{0u, 0u, 0u, 0u}; wy[u] = wd[u];
       if (ok[u]) {
@@ -305,10 +254,34 @@ static inline uint32_t bn_wide_blocks(int64_t R, int C) {
 }
 }  // namespace
 
-extern "C" size_t dl_bn_workspace_bytes(int64_t R, int64_t C) {
-  const int rpb = bn_rows_per_block(R, C);
-  const int64_t chunks = (R + rpb - 1) / rpb;
-  return (size_t)chunks * 2 * (size_t)C * sizeof(float);
+extern "C" size_t dl_bn_workspace_bytes(int64_t R, int64_t C) { return bn_workspace_bytes(R, C); }
+
+// First stage of a column reduction: bn_partial_*<MODE> over (a, y) into ws; *ck_out = the chunking it ran with.  The caller has
+// checked its pointers and C; the checks here come in the order of every entry: dtype, R, window, workspace.  prelu_g / prelu_b
+// (dl_bn_relu_bwd) exist in the generic kernels only.
+template <int MODE>
+static int bn_partials_run(const char* who, const void* a, const void* y, const float* mean, const float* rstd, int64_t R, int64_t C,
+                           int64_t win, int64_t halo, int64_t valid, const float* rw, const float* prelu_g, const float* prelu_b,
+                           int32_t dtype, void* ws, size_t ws_bytes, hipStream_t s, BnChunks* ck_out) {
+  BN_TRY(bn_check_dtype(who, dtype));
+  BN_TRY(bn_check_rows31(who, R));
+  BN_TRY(bn_check_window(who, win, halo, valid));
+  BN_TRY(bn_check_workspace(who, R, C, ws, ws_bytes));
+  if (rw) { win = 0; halo = 0; valid = 0; }
+  const BnChunks ck = bn_chunks(R, C);
+  const bool wide = !prelu_g && bn_wide(dtype, C, a, y);
+  const dim3 grid = bn_partial_grid(C, ck, wide);
+  if (wide)
+    hipLaunchKernelGGL((bn_partial_wide_kernel<MODE>), grid, dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)y, mean, rstd, R, (int)C,
+                       win, halo, valid, rw, (float*)ws, ck.rows);
+  else if (dtype == DL_BF16)
+    hipLaunchKernelGGL((bn_partial_kernel<bf16_t, MODE>), grid, dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)y, mean, rstd, R, (int)C,
+                       win, halo, valid, rw, (float*)ws, ck.rows, prelu_g, prelu_b);
+  else
+    hipLaunchKernelGGL((bn_partial_kernel<float, MODE>), grid, dim3(256), 0, s, (const float*)a, (const float*)y, mean, rstd, R, (int)C,
+                       win, halo, valid, rw, (float*)ws, ck.rows, prelu_g, prelu_b);
+  *ck_out = ck;
+  return DL_OK;
 }
 
 template <int MODE>
@@ -316,22 +289,9 @@ static int bn_reduce(const char* who, const void* a, const void* y, const float*
                      int64_t C, int64_t win, int64_t halo, int64_t valid, const float* rw, int32_t dtype, float* sums, void* ws,
                      size_t ws_bytes, hipStream_t s) {
   DL_CHECK_ARG(a && sums && R > 0 && C > 0 && C % 4 == 0, DL_ERR_ARG, "%s: bad args", who);
-  DL_CHECK_ARG(R < (1ll << 31), DL_ERR_SHAPE, "%s: R must fit 31 bits", who);
-  DL_CHECK_ARG(ws && ws_bytes >= dl_bn_workspace_bytes(R, C), DL_ERR_WORKSPACE, "%s: workspace too small", who);
-  const int rpb = bn_rows_per_block(R, C);
-  const int chunks = (int)((R + rpb - 1) / rpb);
-  dim3 grid((uint32_t)((C + 255) / 256), (uint32_t)chunks);
-  if (dtype == DL_BF16 && (C == 64 || C == 128 || C == 256) && ((uintptr_t)a & 15) == 0 && (!y || ((uintptr_t)y & 15) == 0))
-    hipLaunchKernelGGL((bn_partial_wide_kernel<MODE>), dim3(1, (uint32_t)chunks), dim3(256), 0, s, (const bf16_t*)a,
-                       (const bf16_t*)y, mean, rstd, R, (int)C, win, halo, valid, rw, (float*)ws, rpb);
-  else if (dtype == DL_BF16)
-    hipLaunchKernelGGL((bn_partial_kernel<bf16_t, MODE>), grid, dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)y,
-                       mean, rstd, R, (int)C, win, halo, valid, rw, (float*)ws, rpb);
-  else
-    hipLaunchKernelGGL((bn_partial_kernel<float, MODE>), grid, dim3(256), 0, s, (const float*)a, (const float*)y, mean,
-                       rstd, R, (int)C, win, halo, valid, rw, (float*)ws, rpb);
-  hipLaunchKernelGGL(dl_reduce_partials_kernel, dim3((uint32_t)((2 * C + DL_REDUCE_COLS - 1) / DL_REDUCE_COLS)), dim3(1024), 0, s, (const float*)ws,
-                     chunks, (int64_t)(2 * C), (int)(2 * C), sums, 0);
+  BnChunks ck;
+  BN_TRY(bn_partials_run<MODE>(who, a, y, mean, rstd, R, C, win, halo, valid, rw, nullptr, nullptr, dtype, ws, ws_bytes, s, &ck));
+  bn_reduce_partials(ws, ck, C, sums, s);
   DL_CHECK_LAUNCH(who);
   return DL_OK;
 }
@@ -365,79 +325,84 @@ extern "C" int dl_bn_bwd_reduce_rw(const void* dz, const void* y, const float* m
                       workspace_bytes, (hipStream_t)stream);
 }
 
-static int bn_apply_fwd_run(const void* y, void* z, const float* mean, const float* rstd, const float* gamma,
+// z = BN(y) under the row rule; relu: z = max(0, BN(y)) (generic kernels only).  Checks, launch and launch check for `who`.
+static int bn_apply_fwd_run(const char* who, const void* y, void* z, const float* mean, const float* rstd, const float* gamma,
                             const float* beta, int64_t R, int64_t C, int64_t win, int64_t halo, int64_t valid,
-                            const float* rw, int32_t dtype, dl_stream stream) {
+                            const float* rw, bool relu, int32_t dtype, dl_stream stream) {
   hipStream_t s = (hipStream_t)stream;
-  DL_CHECK_ARG(R < (1ll << 31) && R * (C / 4) < (1ll << 32), DL_ERR_SHAPE, "dl_bn_apply_fwd: R * C / 4 must fit 32 bits");
-  DL_CHECK_ARG(y && z && mean && rstd && gamma && beta && R > 0 && C > 0 && C % 4 == 0, DL_ERR_ARG,
-               "dl_bn_apply_fwd: bad args");
-  const int64_t n = R * (C / 4);
-  const uint32_t blocks = (uint32_t)((n + 255) / 256);
-  const bool wide = dtype == DL_BF16 && (C == 64 || C == 128 || C == 256) && (((uintptr_t)y | (uintptr_t)z) & 15) == 0;
-  if (wide) {
-    const uint32_t wb = bn_wide_blocks(R, (int)C);
-    if (C == 64) hipLaunchKernelGGL((bn_apply_fwd_wide_kernel<64>), dim3(wb), dim3(256), 0, s, (const bf16_t*)y, (bf16_t*)z, mean, rstd, gamma, beta, (int)R, (int)win, (int)halo, (int)valid, rw);
-    else if (C == 128) hipLaunchKernelGGL((bn_apply_fwd_wide_kernel<128>), dim3(wb), dim3(256), 0, s, (const bf16_t*)y, (bf16_t*)z, mean, rstd, gamma, beta, (int)R, (int)win, (int)halo, (int)valid, rw);
-    else hipLaunchKernelGGL((bn_apply_fwd_wide_kernel<256>), dim3(wb), dim3(256), 0, s, (const bf16_t*)y, (bf16_t*)z, mean, rstd, gamma, beta, (int)R, (int)win, (int)halo, (int)valid, rw);
-  } else if (dtype == DL_BF16)
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)y, (bf16_t*)z, mean,
-                       rstd, gamma, beta, R, (int)C, win, halo, valid, rw);
-  else
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<float>), dim3(blocks), dim3(256), 0, s, (const float*)y, (float*)z, mean,
-                       rstd, gamma, beta, R, (int)C, win, halo, valid, rw);
-  DL_CHECK_LAUNCH("dl_bn_apply_fwd");
+  BN_TRY(bn_check_quads32(who, R, C));
+  DL_CHECK_ARG(y && z && mean && rstd && gamma && beta && R > 0 && C > 0 && C % 4 == 0, DL_ERR_ARG, "%s: bad args", who);
+  BN_TRY(bn_check_dtype(who, dtype));
+  BN_TRY(bn_check_window(who, win, halo, valid));
+  const dim3 blocks((uint32_t)((R * (C / 4) + 255) / 256));
+  auto generic = [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((relu ? bn_apply_fwd_kernel<T, true> : bn_apply_fwd_kernel<T, false>), blocks, dim3(256), 0, s, (const T*)y, (T*)z,
+                       mean, rstd, gamma, beta, R, (int)C, win, halo, valid, rw);
+  };
+  if (!relu && bn_wide(dtype, C, y, z))
+    bn_wide_columns(C, [&](auto c) {
+      hipLaunchKernelGGL((bn_apply_fwd_wide_kernel<decltype(c)::value>), dim3(bn_wide_blocks(R, (int)C)), dim3(256), 0, s, (const bf16_t*)y,
+                         (bf16_t*)z, mean, rstd, gamma, beta, (int)R, (int)win, (int)halo, (int)valid, rw);
+    });
+  else if (dtype == DL_BF16) generic(bf16_t{});
+  else generic(float{});
+  DL_CHECK_LAUNCH(who);
   return DL_OK;
 }
 
 extern "C" int dl_bn_apply_fwd(const void* y, void* z, const float* mean, const float* rstd, const float* gamma,
                                const float* beta, int64_t R, int64_t C, int64_t win, int64_t halo, int64_t valid,
                                int32_t dtype, dl_stream stream) {
-  return bn_apply_fwd_run(y, z, mean, rstd, gamma, beta, R, C, win, halo, valid, nullptr, dtype, stream);
+  return bn_apply_fwd_run("dl_bn_apply_fwd", y, z, mean, rstd, gamma, beta, R, C, win, halo, valid, nullptr, false, dtype, stream);
 }
 
 extern "C" int dl_bn_apply_fwd_rw(const void* y, void* z, const float* mean, const float* rstd, const float* gamma,
                                   const float* beta, int64_t R, int64_t C, const float* row_w, int32_t dtype, dl_stream stream) {
   DL_CHECK_ARG(row_w, DL_ERR_ARG, "dl_bn_apply_fwd_rw: null row weights");
-  return bn_apply_fwd_run(y, z, mean, rstd, gamma, beta, R, C, 0, 0, 0, row_w, dtype, stream);
+  return bn_apply_fwd_run("dl_bn_apply_fwd_rw", y, z, mean, rstd, gamma, beta, R, C, 0, 0, 0, row_w, false, dtype, stream);
 }
 
-static int bn_bwd_apply_run(const void* dz, const void* y, const float* mean, const float* rstd, const float* gamma,
-                            const float* sums, float inv_n, int32_t relu_mask, void* dy, int64_t R, int64_t C,
-                            int64_t win, int64_t halo, int64_t valid, const float* rw, int32_t dtype, dl_stream stream) {
+// dy from (dz, y, sums) under the row rule; prelu_b: beta of a BatchNorm -> ReLU (generic kernels only).  Checks, launch and
+// launch check for `who`.
+static int bn_bwd_apply_run(const char* who, const void* dz, const void* y, const float* mean, const float* rstd, const float* gamma,
+                            const float* sums, float inv_n, int32_t relu_mask, void* dy, int64_t R, int64_t C, int64_t win,
+                            int64_t halo, int64_t valid, const float* rw, const float* prelu_b, int32_t dtype, dl_stream stream) {
   hipStream_t s = (hipStream_t)stream;
-  DL_CHECK_ARG(R < (1ll << 31) && R * (C / 4) < (1ll << 32), DL_ERR_SHAPE, "dl_bn_bwd_apply: R * C / 4 must fit 32 bits");
-  DL_CHECK_ARG(dz && y && mean && rstd && gamma && sums && dy && R > 0 && C > 0 && C % 4 == 0, DL_ERR_ARG,
-               "dl_bn_bwd_apply: bad args");
-  const int64_t n = R * (C / 4);
-  const uint32_t blocks = (uint32_t)((n + 255) / 256);
-  const bool wide = dtype == DL_BF16 && (C == 64 || C == 128 || C == 256) && (((uintptr_t)y | (uintptr_t)dz | (uintptr_t)dy) & 15) == 0;
-  if (wide) {
-    const uint32_t wb = bn_wide_blocks(R, (int)C);
-    if (C == 64) hipLaunchKernelGGL((bn_bwd_apply_wide_kernel<64>), dim3(wb), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y, mean, rstd, gamma, sums, inv_n, relu_mask, (bf16_t*)dy, (int)R, (int)win, (int)halo, (int)valid, rw);
-    else if (C == 128) hipLaunchKernelGGL((bn_bwd_apply_wide_kernel<128>), dim3(wb), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y, mean, rstd, gamma, sums, inv_n, relu_mask, (bf16_t*)dy, (int)R, (int)win, (int)halo, (int)valid, rw);
-    else hipLaunchKernelGGL((bn_bwd_apply_wide_kernel<256>), dim3(wb), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y, mean, rstd, gamma, sums, inv_n, relu_mask, (bf16_t*)dy, (int)R, (int)win, (int)halo, (int)valid, rw);
-  } else if (dtype == DL_BF16)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y,
-                       mean, rstd, gamma, sums, inv_n, relu_mask, (bf16_t*)dy, R, (int)C, win, halo, valid, rw);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<float>), dim3(blocks), dim3(256), 0, s, (const float*)dz, (const float*)y,
-                       mean, rstd, gamma, sums, inv_n, relu_mask, (float*)dy, R, (int)C, win, halo, valid, rw);
-  DL_CHECK_LAUNCH("dl_bn_bwd_apply");
+  BN_TRY(bn_check_quads32(who, R, C));
+  DL_CHECK_ARG(dz && y && mean && rstd && gamma && sums && dy && R > 0 && C > 0 && C % 4 == 0, DL_ERR_ARG, "%s: bad args", who);
+  BN_TRY(bn_check_dtype(who, dtype));
+  BN_TRY(bn_check_window(who, win, halo, valid));
+  const dim3 blocks((uint32_t)((R * (C / 4) + 255) / 256));
+  auto generic = [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), blocks, dim3(256), 0, s, (const T*)dz, (const T*)y, mean, rstd, gamma, sums, inv_n,
+                       relu_mask, (T*)dy, R, (int)C, win, halo, valid, rw, prelu_b);
+  };
+  if (!prelu_b && bn_wide(dtype, C, y, dz, dy))
+    bn_wide_columns(C, [&](auto c) {
+      hipLaunchKernelGGL((bn_bwd_apply_wide_kernel<decltype(c)::value>), dim3(bn_wide_blocks(R, (int)C)), dim3(256), 0, s, (const bf16_t*)dz,
+                         (const bf16_t*)y, mean, rstd, gamma, sums, inv_n, relu_mask, (bf16_t*)dy, (int)R, (int)win, (int)halo, (int)valid, rw);
+    });
+  else if (dtype == DL_BF16) generic(bf16_t{});
+  else generic(float{});
+  DL_CHECK_LAUNCH(who);
   return DL_OK;
 }
 
 extern "C" int dl_bn_bwd_apply(const void* dz, const void* y, const float* mean, const float* rstd, const float* gamma,
                                const float* sums, float inv_n, int32_t relu_mask, void* dy, int64_t R, int64_t C,
                                int64_t win, int64_t halo, int64_t valid, int32_t dtype, dl_stream stream) {
-  return bn_bwd_apply_run(dz, y, mean, rstd, gamma, sums, inv_n, relu_mask, dy, R, C, win, halo, valid, nullptr, dtype, stream);
+  return bn_bwd_apply_run("dl_bn_bwd_apply", dz, y, mean, rstd, gamma, sums, inv_n, relu_mask, dy, R, C, win, halo, valid, nullptr,
+                          nullptr, dtype, stream);
 }
 
 extern "C" int dl_bn_bwd_apply_rw(const void* dz, const void* y, const float* mean, const float* rstd, const float* gamma,
                                   const float* sums, float inv_n, int32_t relu_mask, void* dy, int64_t R, int64_t C,
                                   const float* row_w, int32_t dtype, dl_stream stream) {
   DL_CHECK_ARG(row_w, DL_ERR_ARG, "dl_bn_bwd_apply_rw: null row weights");
-  return bn_bwd_apply_run(dz, y, mean, rstd, gamma, sums, inv_n, relu_mask, dy, R, C, 0, 0, 0, row_w, dtype, stream);
+  return bn_bwd_apply_run("dl_bn_bwd_apply_rw", dz, y, mean, rstd, gamma, sums, inv_n, relu_mask, dy, R, C, 0, 0, 0, row_w, nullptr, dtype,
+                          stream);
 }
 
 // ---- weighted tail rows (MolecularGCN's compact padding form) ------------------------------------------------------
@@ -473,7 +438,7 @@ extern "C" int dl_bn_tail_fix(void* dy, const void* y, const float* mean, const 
   hipStream_t s = (hipStream_t)stream;
   DL_CHECK_ARG(dy && y && mean && rstd && gamma && sums && R > 0 && C > 0 && C % 4 == 0 && win > 0 && lead >= 0 && lead < win &&
                    R % win == 0 && w >= 1, DL_ERR_ARG, "dl_bn_tail_fix: bad args");
-  DL_CHECK_ARG(dtype == DL_BF16 || dtype == DL_F32, DL_ERR_ARG, "dl_bn_tail_fix: bad dtype");
+  BN_TRY(bn_check_dtype("dl_bn_tail_fix", dtype));
   const int64_t n = (R / win) * (win - lead) * (C / 4);
   const uint32_t blocks = (uint32_t)((n + 255) / 256);
   if (dtype == DL_BF16)
@@ -566,24 +531,11 @@ extern "C" int dl_bn_stats_finalize(const void* y, int64_t R, int64_t C, int64_t
                                     float* rstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes, dl_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   DL_CHECK_ARG(y && mean && var && rstd && R > 0 && C > 0 && C % 4 == 0 && n > 0, DL_ERR_ARG, "dl_bn_stats_finalize: bad args");
-  DL_CHECK_ARG(R < (1ll << 31), DL_ERR_SHAPE, "dl_bn_stats_finalize: R must fit 31 bits");
-  DL_CHECK_ARG(ws && ws_bytes >= dl_bn_workspace_bytes(R, C), DL_ERR_WORKSPACE, "dl_bn_stats_finalize: workspace too small");
-  const int rpb = bn_rows_per_block(R, C);
-  const int chunks = (int)((R + rpb - 1) / rpb);
-  dim3 grid((uint32_t)((C + 255) / 256), (uint32_t)chunks);
-  if (row_w) { win = 0; halo = 0; valid = 0; }
-  if (dtype == DL_BF16 && (C == 64 || C == 128 || C == 256) && ((uintptr_t)y & 15) == 0)
-    hipLaunchKernelGGL((bn_partial_wide_kernel<0>), dim3(1, (uint32_t)chunks), dim3(256), 0, s, (const bf16_t*)y, (const bf16_t*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, R, (int)C, win, halo, valid, row_w, (float*)ws, rpb);
-  else if (dtype == DL_BF16)
-    hipLaunchKernelGGL((bn_partial_kernel<bf16_t, 0>), grid, dim3(256), 0, s, (const bf16_t*)y, (const bf16_t*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, R, (int)C, win, halo, valid, row_w, (float*)ws, rpb);
-  else if (dtype == DL_F32)
-    hipLaunchKernelGGL((bn_partial_kernel<float, 0>), grid, dim3(256), 0, s, (const float*)y, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, R, (int)C, win, halo, valid, row_w, (float*)ws, rpb);
-  else { dl_set_error("dl_bn_stats_finalize: bad dtype"); return DL_ERR_ARG; }
+  BnChunks ck;
+  BN_TRY(bn_partials_run<0>("dl_bn_stats_finalize", y, nullptr, nullptr, nullptr, R, C, win, halo, valid, row_w, nullptr, nullptr, dtype, ws,
+                            ws_bytes, s, &ck));
   const float unbias = n > 1 ? (float)((double)n / (double)(n - 1)) : 1.f;
-  hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3((uint32_t)((C + 7) / 8)), dim3(1024), 0, s, (const float*)ws, chunks, (int)C,
+  hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3((uint32_t)((C + 7) / 8)), dim3(1024), 0, s, (const float*)ws, ck.chunks, (int)C,
                      (float)(1.0 / (double)n), unbias, eps, momentum, sums, mean, var, rstd, running_mean, running_var);
   DL_CHECK_LAUNCH("dl_bn_stats_finalize");
   return DL_OK;
@@ -595,47 +547,18 @@ extern "C" int dl_bn_stats_finalize(const void* y, int64_t R, int64_t C, int64_t
 // from y (z > 0 <=> (y - mean) rstd gamma + beta > 0), so nothing extra is saved. ----------------------------------------------
 extern "C" int dl_bn_apply_relu_fwd(const void* y, void* z, const float* mean, const float* rstd, const float* gamma, const float* beta,
                                     int64_t R, int64_t C, int32_t dtype, dl_stream stream) {
-  hipStream_t s = (hipStream_t)stream;
-  DL_CHECK_ARG(R < (1ll << 31) && R * (C / 4) < (1ll << 32), DL_ERR_SHAPE, "dl_bn_apply_relu_fwd: R * C / 4 must fit 32 bits");
-  DL_CHECK_ARG(y && z && mean && rstd && gamma && beta && R > 0 && C > 0 && C % 4 == 0, DL_ERR_ARG, "dl_bn_apply_relu_fwd: bad args");
-  const uint32_t blocks = (uint32_t)((R * (C / 4) + 255) / 256);
-  if (dtype == DL_BF16)
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<bf16_t, true>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)y, (bf16_t*)z, mean, rstd, gamma,
-                       beta, R, (int)C, (int64_t)0, (int64_t)0, (int64_t)0, (const float*)nullptr);
-  else if (dtype == DL_F32)
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<float, true>), dim3(blocks), dim3(256), 0, s, (const float*)y, (float*)z, mean, rstd, gamma,
-                       beta, R, (int)C, (int64_t)0, (int64_t)0, (int64_t)0, (const float*)nullptr);
-  else { dl_set_error("dl_bn_apply_relu_fwd: bad dtype"); return DL_ERR_ARG; }
-  DL_CHECK_LAUNCH("dl_bn_apply_relu_fwd");
-  return DL_OK;
+  return bn_apply_fwd_run("dl_bn_apply_relu_fwd", y, z, mean, rstd, gamma, beta, R, C, 0, 0, 0, nullptr, true, dtype, stream);
 }
 
+// partial sums and the apply pass on the generic kernels, which take the pre-ReLU parameters (gamma, beta)
 extern "C" int dl_bn_relu_bwd(const void* dz, const void* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
                               float inv_n, void* dy, float* sums, int64_t R, int64_t C, int32_t dtype, void* ws, size_t ws_bytes,
                               dl_stream stream) {
-  hipStream_t s = (hipStream_t)stream;
-  DL_CHECK_ARG(dz && y && mean && rstd && gamma && beta && dy && sums && R > 0 && C > 0 && C % 4 == 0, DL_ERR_ARG, "dl_bn_relu_bwd: bad args");
-  DL_CHECK_ARG(R < (1ll << 31) && R * (C / 4) < (1ll << 32), DL_ERR_SHAPE, "dl_bn_relu_bwd: R * C / 4 must fit 32 bits");
-  DL_CHECK_ARG(dtype == DL_BF16 || dtype == DL_F32, DL_ERR_ARG, "dl_bn_relu_bwd: bad dtype");
-  DL_CHECK_ARG(ws && ws_bytes >= dl_bn_workspace_bytes(R, C), DL_ERR_WORKSPACE, "dl_bn_relu_bwd: workspace too small");
-  const int rpb = bn_rows_per_block(R, C);
-  const int chunks = (int)((R + rpb - 1) / rpb);
-  dim3 grid((uint32_t)((C + 255) / 256), (uint32_t)chunks);
-  const uint32_t blocks = (uint32_t)((R * (C / 4) + 255) / 256);
-  if (dtype == DL_BF16)
-    hipLaunchKernelGGL((bn_partial_kernel<bf16_t, 1>), grid, dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y, mean, rstd, R, (int)C,
-                       (int64_t)0, (int64_t)0, (int64_t)0, (const float*)nullptr, (float*)ws, rpb, gamma, beta);
-  else
-    hipLaunchKernelGGL((bn_partial_kernel<float, 1>), grid, dim3(256), 0, s, (const float*)dz, (const float*)y, mean, rstd, R, (int)C,
-                       (int64_t)0, (int64_t)0, (int64_t)0, (const float*)nullptr, (float*)ws, rpb, gamma, beta);
-  hipLaunchKernelGGL(dl_reduce_partials_kernel, dim3((uint32_t)((2 * C + DL_REDUCE_COLS - 1) / DL_REDUCE_COLS)), dim3(1024), 0, s, (const float*)ws,
-                     chunks, (int64_t)(2 * C), (int)(2 * C), sums, 0);
-  if (dtype == DL_BF16)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y, mean, rstd, gamma,
-                       (const float*)sums, inv_n, 0, (bf16_t*)dy, R, (int)C, (int64_t)0, (int64_t)0, (int64_t)0, (const float*)nullptr, beta);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<float>), dim3(blocks), dim3(256), 0, s, (const float*)dz, (const float*)y, mean, rstd, gamma,
-                       (const float*)sums, inv_n, 0, (float*)dy, R, (int)C, (int64_t)0, (int64_t)0, (int64_t)0, (const float*)nullptr, beta);
-  DL_CHECK_LAUNCH("dl_bn_relu_bwd");
-  return DL_OK;
+  const char* who = "dl_bn_relu_bwd";
+  DL_CHECK_ARG(dz && y && mean && rstd && gamma && beta && dy && sums && R > 0 && C > 0 && C % 4 == 0, DL_ERR_ARG, "%s: bad args", who);
+  BN_TRY(bn_check_quads32(who, R, C));
+  BnChunks ck;
+  BN_TRY(bn_partials_run<1>(who, dz, y, mean, rstd, R, C, 0, 0, 0, nullptr, gamma, beta, dtype, ws, ws_bytes, (hipStream_t)stream, &ck));
+  bn_reduce_partials(ws, ck, C, sums, (hipStream_t)stream);
+  return bn_bwd_apply_run(who, dz, y, mean, rstd, gamma, sums, inv_n, 0, dy, R, C, 0, 0, 0, nullptr, beta, dtype, stream);
 }

@@ -6,26 +6,9 @@
 //   sums[0..C) = sum_r g,   sums[C..2C) = sum_r g yhat     over the rows that take part.
 // Row weights mark excluded rows (< 0) and nothing else: a compact row's dz already is the sum over the rows it stands for and
 // yhat is shared by them, so the unweighted sum over the compact rows is the sum over the expanded ones.
-#include "common.cuh"
+#include "bn_rows.cuh"
 
 namespace {
-// (the chunking rule of bn.hip's partial-sum kernels: the partials fit dl_bn_workspace_bytes(R, C); the host checks it)
-static inline int bn_eval_rows_per_block(int64_t R, int64_t C) {
-  const int64_t colgroups = (C + 255) / 256;
-  int64_t chunks = (1024 + colgroups - 1) / colgroups;
-  int64_t rows = (R + chunks - 1) / chunks;
-  if (rows < 32) rows = 32;
-  return (int)((rows + 3) / 4 * 4);
-}
-
-// true: the row takes part.  32-bit modulo on purpose, as in bn.hip (R < 2^31 is checked by the host)
-__device__ __forceinline__ bool bn_eval_row_in(const float* __restrict__ rw, int64_t r, int64_t win, int64_t halo, int64_t valid) {
-  if (rw) return rw[r] >= 0.f;
-  if (win == 0) return true;
-  const uint32_t q = (uint32_t)r % (uint32_t)win;
-  return q >= (uint32_t)halo && q < (uint32_t)(halo + valid);
-}
-
 // Generic form.  grid (ceil(C/256), chunks): lane -> 4 columns, wave w -> rows r0 + w, r0 + w + 4, ... of the workgroup's chunk.
 // SUMS: partial[chunk][2][C] = the chunk's (sum g | sum g yhat), summed over the four waves in a fixed order.
 template <typename T, bool SUMS>
@@ -48,7 +31,7 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const T* __restrict__ 
     if (relu_out) bt = *reinterpret_cast<const f32x4*>(beta + c);
     for (int64_t r = r0 + wave; r < r1; r += 4) {
       f32x4 o = {0.f, 0.f, 0.f, 0.f};                      // excluded rows: never read, written as zeros
-      if (bn_eval_row_in(rw, r, win, halo, valid)) {
+      if (bn_row_in(rw, r, win, halo, valid)) {
         f32x4 d = load4<T>(dz + r * C + c);
         const f32x4 yv = load4<T>(y + r * C + c);
         const f32x4 yh = (yv - mu) * rs;
@@ -67,24 +50,13 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const T* __restrict__ 
     }
   }
   if (!SUMS) return;
-  red[0][wave][lane] = s0; red[1][wave][lane] = s1;
-  __syncthreads();
-  if (wave == 0 && c < C) {
-    s0 = red[0][0][lane] + red[0][1][lane] + red[0][2][lane] + red[0][3][lane];
-    s1 = red[1][0][lane] + red[1][1][lane] + red[1][2][lane] + red[1][3][lane];
-    *reinterpret_cast<f32x4*>(partial + ((int64_t)blockIdx.y * 2 + 0) * C + c) = s0;
-    *reinterpret_cast<f32x4*>(partial + ((int64_t)blockIdx.y * 2 + 1) * C + c) = s1;
-  }
+  bn_store_partials(red, s0, s1, lane, wave, c, C, partial);
 }
 
 // Wide form (bf16, C in {64, 128, 256}, 16-byte bases).  grid (1, chunks).  A thread keeps ONE 8-column chunk (16 bytes) for the
 // whole launch, so the per-column parameters are loaded once; 256 / (C/8) rows per pass, four passes in flight: the loads of
 // dz and y of four rows are issued before the first is used.  Partial layout as above.
 constexpr int BN_EVAL_U = 4;
-__device__ __forceinline__ void bn_eval_unpack8(u32x4 w, float (&f)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { f[2 * i] = bf16lo(w[i]); f[2 * i + 1] = bf16hi(w[i]); }
-}
 
 // RELU_OUT is a template parameter here (a flag in the generic form): without it gamma and beta are not kept, and the kernel
 // stays within the 128 registers of four workgroups per CU without scratch (with it: three).
@@ -114,7 +86,7 @@ __global__ __launch_bounds__(256, RELU_OUT ? 3 : 4) void bn_eval_bwd_wide_kernel
 #pragma unroll
     for (int u = 0; u < BN_EVAL_U; ++u) {
       const int64_t rr = r + (int64_t)u * rpp;
-      ok[u] = rr < r1 && bn_eval_row_in(rw, rr, win, halo, valid);
+      ok[u] = rr < r1 && bn_row_in(rw, rr, win, halo, valid);
       wd[u] = u32x4{0u, 0u, 0u, 0u}; wy[u] = wd[u];
       if (ok[u]) {
         wd[u] = *reinterpret_cast<const u32x4*>(dz + rr * C + c);
@@ -128,8 +100,8 @@ __global__ __launch_bounds__(256, RELU_OUT ? 3 : 4) void bn_eval_bwd_wide_kernel
       u32x4 o = {0u, 0u, 0u, 0u};                           // excluded rows: never read, written as zeros
       if (ok[u]) {
         float d[8], yv[8];
-        bn_eval_unpack8(wd[u], d);
-        bn_eval_unpack8(wy[u], yv);
+        unpack8(wd[u], d);
+        unpack8(wy[u], yv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float yh = (yv[e] - mu[e]) * rs[e];                  // same operation order as the generic form
@@ -140,34 +112,13 @@ __global__ __launch_bounds__(256, RELU_OUT ? 3 : 4) void bn_eval_bwd_wide_kernel
           if (relu_in) v = yv[e] > 0.f ? v : 0.f;
           d[e] = v;
         }
-        o = u32x4{pack_bf16x2(d[0], d[1]), pack_bf16x2(d[2], d[3]), pack_bf16x2(d[4], d[5]), pack_bf16x2(d[6], d[7])};
+        o = pack8(d);
       }
       store16_fam<2>(dy + rr * C + c, o);
     }
   }
   if (!SUMS) return;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { red[0][tid][e] = s0[e]; red[1][tid][e] = s1[e]; }
-  __syncthreads();
-  // thread t < 2*C sums column (t % C) of array (t / C) over the rpp row groups, in a fixed order
-  for (int t = tid; t < 2 * C; t += 256) {
-    const int which = t / C, col = t % C, cch = col >> 3, e = col & 7;
-    float acc = 0.f;
-    for (int g = 0; g < rpp; ++g) acc += red[which][g * cpr + cch][e];
-    partial[((int64_t)blockIdx.y * 2 + which) * C + col] = acc;
-  }
-}
-
-template <typename T>
-static void bn_eval_launch_generic(bool with_sums, dim3 grid, hipStream_t s, const void* dz, const void* y, const float* mean,
-                                   const float* rstd, const float* gamma, const float* beta, int relu_in, int relu_out, void* dy, int64_t R,
-                                   int C, int64_t win, int64_t halo, int64_t valid, const float* rw, float* ws, int rpb) {
-  if (with_sums)
-    hipLaunchKernelGGL((bn_eval_bwd_kernel<T, true>), grid, dim3(256), 0, s, (const T*)dz, (const T*)y, mean, rstd, gamma, beta, relu_in,
-                       relu_out, (T*)dy, R, C, win, halo, valid, rw, ws, rpb);
-  else
-    hipLaunchKernelGGL((bn_eval_bwd_kernel<T, false>), grid, dim3(256), 0, s, (const T*)dz, (const T*)y, mean, rstd, gamma, beta, relu_in,
-                       relu_out, (T*)dy, R, C, win, halo, valid, rw, ws, rpb);
+  bn_store_partials_wide(red, s0, s1, C, partial);
 }
 }  // namespace
 
@@ -175,41 +126,33 @@ extern "C" int dl_bn_eval_bwd(const void* dz, const void* y, const float* mean, 
                               int32_t relu_in, int32_t relu_out, void* dy, float* sums, int64_t R, int64_t C, int64_t win, int64_t halo,
                               int64_t valid, const float* row_w, int32_t dtype, void* workspace, size_t workspace_bytes, dl_stream stream) {
   hipStream_t s = (hipStream_t)stream;
-  DL_CHECK_ARG(dz && y && mean && rstd && gamma && dy && R > 0 && C > 0 && C % 4 == 0, DL_ERR_ARG, "dl_bn_eval_bwd: bad args");
-  DL_CHECK_ARG(!relu_out || beta, DL_ERR_ARG, "dl_bn_eval_bwd: relu_out needs beta");
-  DL_CHECK_ARG(dy != dz && dy != y, DL_ERR_ARG, "dl_bn_eval_bwd: dy must not alias dz or y");
-  DL_CHECK_ARG(dtype == DL_BF16 || dtype == DL_F32, DL_ERR_ARG, "dl_bn_eval_bwd: bad dtype");
-  DL_CHECK_ARG(R < (1ll << 31), DL_ERR_SHAPE, "dl_bn_eval_bwd: R must fit 31 bits");
-  DL_CHECK_ARG(win >= 0 && halo >= 0 && valid >= 0 && (win == 0 || halo + valid <= win) && win < (1ll << 31), DL_ERR_ARG,
-               "dl_bn_eval_bwd: bad window");
-  if (row_w) { win = 0; halo = 0; valid = 0; }
-  const int rpb = bn_eval_rows_per_block(R, C);
-  const int chunks = (int)((R + rpb - 1) / rpb);
+  const char* who = "dl_bn_eval_bwd";
+  DL_CHECK_ARG(dz && y && mean && rstd && gamma && dy && R > 0 && C > 0 && C % 4 == 0, DL_ERR_ARG, "%s: bad args", who);
+  DL_CHECK_ARG(!relu_out || beta, DL_ERR_ARG, "%s: relu_out needs beta", who);
+  DL_CHECK_ARG(dy != dz && dy != y, DL_ERR_ARG, "%s: dy must not alias dz or y", who);
+  BN_TRY(bn_check_dtype(who, dtype));
+  BN_TRY(bn_check_rows31(who, R));
+  BN_TRY(bn_check_window(who, win, halo, valid));
   const bool with_sums = sums != nullptr;
-  if (with_sums)
-    DL_CHECK_ARG(workspace && workspace_bytes >= dl_bn_workspace_bytes(R, C) &&
-                     workspace_bytes >= (size_t)chunks * 2 * (size_t)C * sizeof(float), DL_ERR_WORKSPACE,
-                 "dl_bn_eval_bwd: workspace too small");
+  if (with_sums) BN_TRY(bn_check_workspace(who, R, C, workspace, workspace_bytes));
+  if (row_w) { win = 0; halo = 0; valid = 0; }
+  const BnChunks ck = bn_chunks(R, C);
   float* ws = with_sums ? (float*)workspace : nullptr;
-  const bool wide = dtype == DL_BF16 && (C == 64 || C == 128 || C == 256) && (((uintptr_t)dz | (uintptr_t)y | (uintptr_t)dy) & 15) == 0;
-  dim3 grid((uint32_t)((C + 255) / 256), (uint32_t)chunks);
+  const bool wide = bn_wide(dtype, C, dz, y, dy);
+  const dim3 grid = bn_partial_grid(C, ck, wide);
+  auto generic = [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((with_sums ? bn_eval_bwd_kernel<T, true> : bn_eval_bwd_kernel<T, false>), grid, dim3(256), 0, s, (const T*)dz,
+                       (const T*)y, mean, rstd, gamma, beta, (int)relu_in, (int)relu_out, (T*)dy, R, (int)C, win, halo, valid, row_w, ws, ck.rows);
+  };
   if (wide) {
-#define BN_EVAL_WIDE(SUMS_, RELU_)                                                                                                   \
-  hipLaunchKernelGGL((bn_eval_bwd_wide_kernel<SUMS_, RELU_>), dim3(1, (uint32_t)chunks), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y, \
-                     mean, rstd, gamma, beta, (int)relu_in, (bf16_t*)dy, R, (int)C, win, halo, valid, row_w, ws, rpb)
-    if (with_sums) { if (relu_out) BN_EVAL_WIDE(true, true); else BN_EVAL_WIDE(true, false); }
-    else { if (relu_out) BN_EVAL_WIDE(false, true); else BN_EVAL_WIDE(false, false); }
-#undef BN_EVAL_WIDE
-  } else if (dtype == DL_BF16) {
-    bn_eval_launch_generic<bf16_t>(with_sums, grid, s, dz, y, mean, rstd, gamma, beta, (int)relu_in, (int)relu_out, dy, R, (int)C, win, halo,
-                                   valid, row_w, ws, rpb);
-  } else {
-    bn_eval_launch_generic<float>(with_sums, grid, s, dz, y, mean, rstd, gamma, beta, (int)relu_in, (int)relu_out, dy, R, (int)C, win, halo,
-                                  valid, row_w, ws, rpb);
-  }
-  if (with_sums)
-    hipLaunchKernelGGL(dl_reduce_partials_kernel, dim3((uint32_t)((2 * C + DL_REDUCE_COLS - 1) / DL_REDUCE_COLS)), dim3(1024), 0, s,
-                       (const float*)ws, chunks, (int64_t)(2 * C), (int)(2 * C), sums, 0);
-  DL_CHECK_LAUNCH("dl_bn_eval_bwd");
+    auto k = with_sums ? (relu_out ? bn_eval_bwd_wide_kernel<true, true> : bn_eval_bwd_wide_kernel<true, false>)
+                       : (relu_out ? bn_eval_bwd_wide_kernel<false, true> : bn_eval_bwd_wide_kernel<false, false>);
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y, mean, rstd, gamma, beta, (int)relu_in, (bf16_t*)dy, R,
+                       (int)C, win, halo, valid, row_w, ws, ck.rows);
+  } else if (dtype == DL_BF16) generic(bf16_t{});
+  else generic(float{});
+  if (with_sums) bn_reduce_partials(ws, ck, C, sums, s);
+  DL_CHECK_LAUNCH(who);
   return DL_OK;
 }

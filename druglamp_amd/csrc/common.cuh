@@ -98,6 +98,19 @@ template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, f32x4 v) {
   u32x2 w = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
   *reinterpret_cast<u32x2*>(p) = w;
 }
+// one 16-byte chunk of 8 bf16 <-> 8 floats (registers; the 16-byte row kernels of norm.hip, bn.hip, bn_eval.hip)
+__device__ __forceinline__ void unpack8(u32x4 w, float (&f)[8]) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    f[2 * e] = bf16lo(w[e]); f[2 * e + 1] = bf16hi(w[e]);
+#ifdef DL_UNPACK_NOP   // (round 6 hazard experiment, tools/hazard_run2.sh: a wait state between the unpacking shift and whatever consumes it)
+    asm volatile("s_nop 1" : "+v"(f[2 * e]));
+#endif
+  }
+}
+__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
+  return u32x4{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
+}
 
 // ---- MFMA wrappers ----------------------------------------------------------------------
 template <typename T> struct Mma;

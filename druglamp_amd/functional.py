@@ -912,9 +912,8 @@ class ProteinCNNFn(torch.autograd.Function):
                 ops.gemm(cur, Wg, M=Mg, N=C, K=k * C, ldx=C, bias=_f32(b), act=2, out=y[pl:pl + Mg])
             if training:
                 # batch statistics + nn.BatchNorm1d's running-stat update (momentum given) in one tiny launch
-                upd = momenta is not None and rmean.dtype == torch.float32
-                mean, var, rstd = ops.bn_stats_finalize(y, LP, _CNN_HALO, Lv, n, eps, momenta[i] if upd else 0.0,
-                                                        rmean.detach() if upd else None, rvar.detach() if upd else None, rw)
+                mom = momenta[i] if momenta is not None else None
+                mean, var, rstd = ops.bn_stats_finalize(y, LP, _CNN_HALO, Lv, n, eps, *_bn_running(mom, rmean, rvar), rw)
             else:
                 mean, var = rmean.detach().float(), rvar.detach().float()
                 rstd = torch.rsqrt(var + eps)
@@ -1306,6 +1305,35 @@ def fill_pool(x: torch.Tensor, site_len: int, out_dtype: torch.dtype):
     return ops.fill_pool(x, site_len, out_dtype)
 
 
+def _bn_running(momentum, rmean, rvar):
+    """(momentum, running_mean, running_var) for ops.bn_finalize / bn_stats_finalize: nn.BatchNorm1d's update, fp32 buffers only."""
+    return (momentum, rmean.detach(), rvar.detach()) if momentum is not None and rmean is not None and rmean.dtype == torch.float32 else (0.0, None, None)
+
+
+def _bn_affine(bn: torch.nn.BatchNorm1d, x2d: torch.Tensor):
+    """(weight, bias) of a BatchNorm1d; affine=False: ones / zeros."""
+    return (bn.weight if bn.weight is not None else torch.ones(x2d.shape[1], device=x2d.device),
+            bn.bias if bn.bias is not None else torch.zeros(x2d.shape[1], device=x2d.device))
+
+
+def _bn_apply_and_save(ctx, x, mean, var, rstd, gamma, beta, relu):
+    """The end of a BatchNorm forward: the apply pass (relu: in the same kernel), the saved tensors, (y, mean, var)."""
+    g, b = gamma.detach().float(), beta.detach().float()
+    y = ops.bn_apply_relu_fwd(x, mean, rstd, g, b) if relu else ops.bn_apply_fwd(x, mean, rstd, g, b, 0, 0, 0)
+    ctx.save_for_backward(x, mean, rstd, g, b if relu else None)
+    ctx.mark_non_differentiable(mean, var)
+    ctx.set_materialize_grads(False)       # no zero-filled gradients for the non-differentiable outputs
+    return y, mean, var
+
+
+def _bn_train_bwd(dy, x, mean, rstd, g, b, inv_n, relu):
+    """Backward on batch statistics: (dx, sums [2C] = (d beta | d gamma)); relu: the ReLU's open set is recomputed from x."""
+    if relu:
+        return ops.bn_relu_bwd(dy, x, mean, rstd, g, b, inv_n)
+    sums = ops.bn_bwd_reduce(dy, x, mean, rstd, 0, 0, 0)
+    return ops.bn_bwd_apply(dy, x, mean, rstd, g, sums, inv_n, False, 0, 0, 0), sums
+
+
 class BatchNormRowsFn(torch.autograd.Function):
     """BatchNorm1d over the rows of a [R][C] matrix (training: batch statistics) on the dl_bn_* kernels.
     Returns (y, mean, var) with biased variance; running-stat bookkeeping stays with the caller."""
@@ -1317,19 +1345,12 @@ class BatchNormRowsFn(torch.autograd.Function):
         R, C = x.shape
         x = x.contiguous()
         if training:
-            upd = momentum is not None and rmean is not None and rmean.dtype == torch.float32
-            mean, var, rstd = ops.bn_stats_finalize(x, 0, 0, 0, R, eps, momentum if upd else 0.0, rmean.detach() if upd else None,
-                                                    rvar.detach() if upd else None)
+            mean, var, rstd = ops.bn_stats_finalize(x, 0, 0, 0, R, eps, *_bn_running(momentum, rmean, rvar))
         else:
             mean, var = rmean.detach().float(), rvar.detach().float()
             rstd = torch.rsqrt(var + eps)
-        g, b = gamma.detach().float(), beta.detach().float()
-        y = ops.bn_apply_relu_fwd(x, mean, rstd, g, b) if relu else ops.bn_apply_fwd(x, mean, rstd, g, b, 0, 0, 0)
-        ctx.save_for_backward(x, mean, rstd, g, b if relu else None)
         ctx.training, ctx.relu = training, relu
-        ctx.mark_non_differentiable(mean, var)
-        ctx.set_materialize_grads(False)       # no zero-filled gradients for the non-differentiable outputs
-        return y, mean, var
+        return _bn_apply_and_save(ctx, x, mean, var, rstd, gamma, beta, relu)
 
     @staticmethod
     def backward(ctx, dy, _m, _v):
@@ -1340,14 +1361,10 @@ class BatchNormRowsFn(torch.autograd.Function):
             # fixed statistics: dx needs no column sums — one pass gives dx and (d beta | d gamma); all parameters frozen
             # (the input gradient of a deployed model): the dx pass alone
             dx, sums = ops.bn_eval_bwd(dy, x, mean, rstd, g, b, relu_out=ctx.relu, want_sums=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-            if sums is None:
-                return dx, None, None, None, None, None, None, None, None
-        elif ctx.relu:
-            dx, sums = ops.bn_relu_bwd(dy, x, mean, rstd, g, b, 1.0 / R)
         else:
-            sums = ops.bn_bwd_reduce(dy, x, mean, rstd, 0, 0, 0)
-            dx = ops.bn_bwd_apply(dy, x, mean, rstd, g, sums, 1.0 / R, False, 0, 0, 0)
-        return dx, sums[C:], sums[:C], None, None, None, None, None, None
+            dx, sums = _bn_train_bwd(dy, x, mean, rstd, g, b, 1.0 / R, ctx.relu)
+        dgamma, dbeta = (sums[C:], sums[:C]) if sums is not None else (None, None)
+        return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
 class BatchNormWeightedTailFn(torch.autograd.Function):
@@ -1368,29 +1385,17 @@ class BatchNormWeightedTailFn(torch.autograd.Function):
         n = (R // LP) * (lead + w * tail)
         sums = ops.bn_stats(x, LP, 0, lead)
         sums = sums.add_(ops.bn_stats(x, LP, lead, tail), alpha=float(w))
-        upd = momentum is not None and rmean is not None and rmean.dtype == torch.float32
-        mean, var, rstd = ops.bn_finalize(sums, n, eps, momentum if upd else 0.0, rmean.detach() if upd else None,
-                                          rvar.detach() if upd else None)
-        g, b = gamma.detach().float(), beta.detach().float()
-        y = ops.bn_apply_relu_fwd(x, mean, rstd, g, b) if relu else ops.bn_apply_fwd(x, mean, rstd, g, b, 0, 0, 0)
-        ctx.save_for_backward(x, mean, rstd, g, b if relu else None)
+        mean, var, rstd = ops.bn_finalize(sums, n, eps, *_bn_running(momentum, rmean, rvar))
         ctx.cfg = (LP, lead, w, n, relu)
-        ctx.mark_non_differentiable(mean, var)
-        ctx.set_materialize_grads(False)
-        return y, mean, var
+        return _bn_apply_and_save(ctx, x, mean, var, rstd, gamma, beta, relu)
 
     @staticmethod
     def backward(ctx, dy, _m, _v):
         x, mean, rstd, g, b = ctx.saved_tensors
         LP, lead, w, n, relu = ctx.cfg
         R, C = x.shape
-        dy = dy.contiguous()
         # (tail rows of dy already hold the sums over their copies; a row and its copies share the ReLU mask)
-        if relu:
-            dx, sums = ops.bn_relu_bwd(dy, x, mean, rstd, g, b, 1.0 / n)
-        else:
-            sums = ops.bn_bwd_reduce(dy, x, mean, rstd, 0, 0, 0)
-            dx = ops.bn_bwd_apply(dy, x, mean, rstd, g, sums, 1.0 / n, False, 0, 0, 0)
+        dx, sums = _bn_train_bwd(dy.contiguous(), x, mean, rstd, g, b, 1.0 / n, relu)
         # tail rows: dx = sum over the w copies of g rstd (dy_copy - mean_dy - xhat mean_dyxhat): the mean terms w times
         ops.bn_tail_fix(dx, x, mean, rstd, g, sums, 1.0 / n, w, LP, lead)
         return dx, sums[C:], sums[:C], None, None, None, None, None, None, None, None
@@ -1426,10 +1431,7 @@ def batch_norm_rows_weighted_tail(bn: torch.nn.BatchNorm1d, x2d: torch.Tensor, L
     weights)."""
     if not bn.training:
         return batch_norm_rows(bn, x2d, relu=relu)
-    C = x2d.shape[1]
-    gam = bn.weight if bn.weight is not None else torch.ones(C, device=x2d.device)      # affine=False
-    bet = bn.bias if bn.bias is not None else torch.zeros(C, device=x2d.device)
-    y, _mean, _var = BatchNormWeightedTailFn.apply(x2d, gam, bet, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
+    y, _mean, _var = BatchNormWeightedTailFn.apply(x2d, *_bn_affine(bn, x2d), bn.running_mean, bn.running_var, bn.eps, bn.momentum,
                                                  LP, lead, w, relu)
     bn_tick(bn.num_batches_tracked)
     return y
@@ -1475,14 +1477,11 @@ def bn_tick(counter: torch.Tensor) -> None:
 
 def batch_norm_rows(bn: torch.nn.BatchNorm1d, x2d: torch.Tensor, relu: bool = False) -> torch.Tensor:
     """nn.BatchNorm1d semantics (incl. running statistics, momentum, unbiased running variance); relu: max(0, .) behind it."""
-    C = x2d.shape[1]
     if bn.training and x2d.shape[0] <= 1:
         # torch.nn.functional.batch_norm's own check and message: batch statistics of ONE row are meaningless (the
         # reference's classifier raises here for a training batch of one pair; a silent NaN would be worse)
         raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(x2d.size()))
-    w = bn.weight if bn.weight is not None else torch.ones(C, device=x2d.device)      # affine=False
-    b = bn.bias if bn.bias is not None else torch.zeros(C, device=x2d.device)
-    y, mean, var = BatchNormRowsFn.apply(x2d, w, b, bn.running_mean, bn.running_var, bn.training, bn.eps,
+    y, mean, var = BatchNormRowsFn.apply(x2d, *_bn_affine(bn, x2d), bn.running_mean, bn.running_var, bn.training, bn.eps,
                                          bn.momentum if bn.training else None, relu)
     if bn.training:
         bn_tick(bn.num_batches_tracked)        # running mean / var were updated by dl_bn_finalize

@@ -1041,18 +1041,25 @@ def triplet_sigcos_bwd(p_lats, d_lats, gt_i8, margin: float, buf, ntri, grad_out
     return dp, dd
 
 
-def bn_stats(y2d, win, halo, valid, rw=None):
-    """rw (R,) fp32 row weights (< 0 halo, 0 context, m >= 1 multiplicity) replace the window rule (dl_bn_stats_rw)."""
+def _bn_entry(name, rw, win, halo, valid):
+    """(C function, its name, its row-rule arguments): rw (R,) fp32 row weights (< 0 halo, 0 context, m >= 1 multiplicity) go to
+    dl_<name>_rw as `row_w`, exactly where dl_<name> takes the window rule `win, halo, valid`."""
+    name, rows = (name + "_rw", (rw.data_ptr(),)) if rw is not None else (name, (win, halo, valid))
+    return getattr(_lib.lib(), name), name, rows
+
+
+def _bn_sums_ws(y2d):
+    """(sums [2C] fp32, the workspace of the partial-sum kernels) for a column reduction over y2d."""
     R, Cc = y2d.shape
-    L = _lib.lib()
     sums = torch.empty(2 * Cc, dtype=torch.float32, device=y2d.device)
-    ws = _ws2.get(L.dl_bn_workspace_bytes(R, Cc), y2d.device)
-    if rw is not None:
-        check(L.dl_bn_stats_rw(y2d.data_ptr(), R, Cc, rw.data_ptr(), _dt(y2d), sums.data_ptr(), ws.data_ptr(), ws.numel(),
-                               _stream()), "dl_bn_stats_rw")
-        return sums
-    check(L.dl_bn_stats(y2d.data_ptr(), R, Cc, win, halo, valid, _dt(y2d), sums.data_ptr(), ws.data_ptr(), ws.numel(),
-                        _stream()), "dl_bn_stats")
+    return sums, _ws2.get(_lib.lib().dl_bn_workspace_bytes(R, Cc), y2d.device)
+
+
+def bn_stats(y2d, win, halo, valid, rw=None):
+    R, Cc = y2d.shape
+    fn, name, rows = _bn_entry("dl_bn_stats", rw, win, halo, valid)
+    sums, ws = _bn_sums_ws(y2d)
+    check(fn(y2d.data_ptr(), R, Cc, *rows, _dt(y2d), sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), name)
     return sums
 
 
@@ -1079,41 +1086,28 @@ def bn_finalize(sums, n, eps, momentum=0.0, running_mean=None, running_var=None)
 
 def bn_apply_fwd(y2d, mean, rstd, gamma, beta, win, halo, valid, rw=None):
     R, Cc = y2d.shape
+    fn, name, rows = _bn_entry("dl_bn_apply_fwd", rw, win, halo, valid)
     z = torch.empty_like(y2d)
-    if rw is not None:
-        check(_lib.lib().dl_bn_apply_fwd_rw(y2d.data_ptr(), z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
-                                            beta.data_ptr(), R, Cc, rw.data_ptr(), _dt(y2d), _stream()), "dl_bn_apply_fwd_rw")
-        return z
-    check(_lib.lib().dl_bn_apply_fwd(y2d.data_ptr(), z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
-                                     beta.data_ptr(), R, Cc, win, halo, valid, _dt(y2d), _stream()), "dl_bn_apply_fwd")
+    check(fn(y2d.data_ptr(), z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), R, Cc, *rows, _dt(y2d),
+             _stream()), name)
     return z
 
 
 def bn_bwd_reduce(dz2d, y2d, mean, rstd, win, halo, valid, rw=None):
     R, Cc = y2d.shape
-    L = _lib.lib()
-    sums = torch.empty(2 * Cc, dtype=torch.float32, device=y2d.device)
-    ws = _ws2.get(L.dl_bn_workspace_bytes(R, Cc), y2d.device)
-    if rw is not None:
-        check(L.dl_bn_bwd_reduce_rw(dz2d.data_ptr(), y2d.data_ptr(), mean.data_ptr(), rstd.data_ptr(), R, Cc, rw.data_ptr(),
-                                    _dt(y2d), sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "dl_bn_bwd_reduce_rw")
-        return sums
-    check(L.dl_bn_bwd_reduce(dz2d.data_ptr(), y2d.data_ptr(), mean.data_ptr(), rstd.data_ptr(), R, Cc, win, halo, valid,
-                             _dt(y2d), sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "dl_bn_bwd_reduce")
+    fn, name, rows = _bn_entry("dl_bn_bwd_reduce", rw, win, halo, valid)
+    sums, ws = _bn_sums_ws(y2d)
+    check(fn(dz2d.data_ptr(), y2d.data_ptr(), mean.data_ptr(), rstd.data_ptr(), R, Cc, *rows, _dt(y2d), sums.data_ptr(), ws.data_ptr(),
+             ws.numel(), _stream()), name)
     return sums
 
 
 def bn_bwd_apply(dz2d, y2d, mean, rstd, gamma, sums, inv_n, relu_mask, win, halo, valid, rw=None):
     R, Cc = y2d.shape
+    fn, name, rows = _bn_entry("dl_bn_bwd_apply", rw, win, halo, valid)
     dy = torch.empty_like(y2d)
-    if rw is not None:
-        check(_lib.lib().dl_bn_bwd_apply_rw(dz2d.data_ptr(), y2d.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
-                                            sums.data_ptr(), float(inv_n), int(relu_mask), dy.data_ptr(), R, Cc, rw.data_ptr(),
-                                            _dt(y2d), _stream()), "dl_bn_bwd_apply_rw")
-        return dy
-    check(_lib.lib().dl_bn_bwd_apply(dz2d.data_ptr(), y2d.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
-                                     sums.data_ptr(), float(inv_n), int(relu_mask), dy.data_ptr(), R, Cc, win, halo, valid,
-                                     _dt(y2d), _stream()), "dl_bn_bwd_apply")
+    check(fn(dz2d.data_ptr(), y2d.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), sums.data_ptr(), float(inv_n),
+             int(relu_mask), dy.data_ptr(), R, Cc, *rows, _dt(y2d), _stream()), name)
     return dy
 
 
@@ -1129,12 +1123,10 @@ def bn_apply_relu_fwd(y2d, mean, rstd, gamma, beta):
 def bn_relu_bwd(dz2d, y2d, mean, rstd, gamma, beta, inv_n):
     """Backward of z = max(0, BN(y)): (dy, sums [2C] = (d beta | d gamma)) (dl_bn_relu_bwd)."""
     R, Cc = y2d.shape
-    L = _lib.lib()
     dy = torch.empty_like(y2d)
-    sums = torch.empty(2 * Cc, dtype=torch.float32, device=y2d.device)
-    ws = _ws2.get(L.dl_bn_workspace_bytes(R, Cc), y2d.device)
-    check(L.dl_bn_relu_bwd(dz2d.data_ptr(), y2d.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                           float(inv_n), dy.data_ptr(), sums.data_ptr(), R, Cc, _dt(y2d), ws.data_ptr(), ws.numel(), _stream()),
+    sums, ws = _bn_sums_ws(y2d)
+    check(_lib.lib().dl_bn_relu_bwd(dz2d.data_ptr(), y2d.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                    float(inv_n), dy.data_ptr(), sums.data_ptr(), R, Cc, _dt(y2d), ws.data_ptr(), ws.numel(), _stream()),
           "dl_bn_relu_bwd")
     return dy, sums
 
@@ -1145,17 +1137,14 @@ def bn_eval_bwd(dz, y, mean, rstd, gamma, beta=None, *, relu_in=False, relu_out=
     None).  relu_out: a ReLU behind the BatchNorm (needs beta); relu_in: y is the output of a ReLU in front of it; row_w < 0
     marks excluded rows and is otherwise not applied (a compact row's dz already is the sum over the rows it stands for)."""
     R, Cc = y.shape
-    L = _lib.lib()
     if relu_out and beta is None:
         raise ValueError("bn_eval_bwd: relu_out needs beta")
     dx = torch.empty_like(y)
-    sums = ws = None
-    if want_sums:
-        sums = torch.empty(2 * Cc, dtype=torch.float32, device=y.device)
-        ws = _ws2.get(L.dl_bn_workspace_bytes(R, Cc), y.device)
-    check(L.dl_bn_eval_bwd(dz.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), _ptr(beta) if relu_out else None,
-                           int(relu_in), int(relu_out), dx.data_ptr(), _ptr(sums), R, Cc, int(win), int(halo), int(valid), _ptr(row_w),
-                           _dt(y), _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "dl_bn_eval_bwd")
+    sums, ws = _bn_sums_ws(y) if want_sums else (None, None)
+    check(_lib.lib().dl_bn_eval_bwd(dz.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+                                    _ptr(beta) if relu_out else None, int(relu_in), int(relu_out), dx.data_ptr(), _ptr(sums), R, Cc, int(win),
+                                    int(halo), int(valid), _ptr(row_w), _dt(y), _ptr(ws), ws.numel() if ws is not None else 0, _stream()),
+          "dl_bn_eval_bwd")
     return dx, sums
 
 
