@@ -823,6 +823,9 @@ class Trainer:
     def check_device_flags(self):
         """Synchronising check of the padding guards (end of an epoch, of an evaluation, of a benchmark)."""
         if torch.device(self.device).type == "cuda":
+            # (the copy of the word that an earlier step posted for _poll_guard is older than what is read here: drop it, or a
+            #  trip raised — and cleared — below would be raised a second time by the next step's poll)
+            self._guard_event = None
             ops.check_guard_flags(self.device)
 
     @staticmethod
