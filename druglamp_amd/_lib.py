@@ -326,6 +326,9 @@ SIGNATURES = {
     "dl_ce_rows_workspace_bytes": (c_sz, [c_i64]),
     "dl_ce_rows_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "dl_ce_rows_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "dl_cls_loss_workspace_bytes": (c_sz, [c_i64]),
+    "dl_cls_loss_fwd": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_sz, C.c_uint32, c_vp, c_vp]),
+    "dl_cls_loss_bwd": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "dl_protein_plan_build": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dl_prof_enable": (c_i32, [c_i32, c_i32]),
     "dl_prof_collect": (c_i32, [c_i32, C.POINTER(c_i64), C.POINTER(C.c_double), C.POINTER(C.c_double),

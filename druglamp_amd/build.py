@@ -80,8 +80,9 @@ def _stale(out, deps):
 # grad_guard.hip gets the flag: its guarded AdamW kernel is elementwise.hip's arithmetic (csrc/adamw.cuh), and the two must give
 # the same bits.
 # ema.hip gets the flag: per-element fp32 on 16-byte vectors, HBM-bound (the packed forms buy nothing) — bn_eval.hip's caution.
+# cls_loss.hip gets the flag: per-element fp32 on a few hundred rows (the packed forms buy nothing) — the same caution.
 FILE_FLAGS = {"norm.hip": ["-fno-slp-vectorize"], "elementwise.hip": ["-fno-slp-vectorize"], "bn_eval.hip": ["-fno-slp-vectorize"],
-              "grad_guard.hip": ["-fno-slp-vectorize"], "ema.hip": ["-fno-slp-vectorize"]}
+              "grad_guard.hip": ["-fno-slp-vectorize"], "ema.hip": ["-fno-slp-vectorize"], "cls_loss.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src, force, objdir=OBJDIR, extra=()):

@@ -1179,6 +1179,47 @@ def ce_rows_bwd(logits2d, labels, C: int, ignore_index: int, lse, out2, grad_out
     return d
 
 
+def _cls_loss_operands(score2d, labels, weights, who):
+    _need_gpu(score2d, labels, weights)
+    if score2d.dim() != 2 or score2d.shape[1] not in (1, 2) or score2d.stride(1) != 1:
+        raise ValueError("%s: score must be (N, 1) or (N, 2) with unit column stride (got %s, strides %s)"
+                         % (who, tuple(score2d.shape), tuple(score2d.stride())))
+    N = score2d.shape[0]
+    for name, t in (("labels", labels), ("weights", weights)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or t.shape != (N,) or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous float32 (%d,) tensor (got %s %s)" % (who, name, N, t.dtype, tuple(t.shape)))
+    return N, score2d.stride(0) if N > 1 else max(score2d.stride(0), score2d.shape[1])
+
+
+def cls_loss_fwd(score2d, labels, weights, a_pos: float, a_neg: float, gamma: float):
+    """Weighted / focal BCE on the logits score2d (N, 1 | 2) (dl_cls_loss_fwd): (out2 = [loss, den], probs (N,) fp32 = sigmoid(z)).
+    labels fp32 (N,), weights fp32 (N,) or None.  A non-finite score, a label outside [0, 1] and a negative or non-finite weight make the
+    loss NaN; the last two also raise FLAG_CLS_LABEL in the loss's device guard word (cls_loss_flags; check_guard_flags reports it)."""
+    N, ld = _cls_loss_operands(score2d, labels, weights, "cls_loss_fwd")
+    L = _lib.lib()
+    dev = score2d.device
+    probs = torch.empty(N, dtype=torch.float32, device=dev)
+    out2 = torch.empty(2, dtype=torch.float32, device=dev)
+    nws = L.dl_cls_loss_workspace_bytes(N)
+    ws = _ws2.get(nws, dev) if nws else None             # (the one-workgroup form takes none)
+    check(L.dl_cls_loss_fwd(score2d.data_ptr(), ld, score2d.shape[1], _dt(score2d), labels.data_ptr(), _ptr(weights), N, float(a_pos),
+                            float(a_neg), float(gamma), probs.data_ptr(), out2.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0,
+                            FLAG_CLS_LABEL, cls_loss_flags(dev).data_ptr(), _stream()), "dl_cls_loss_fwd")
+    return out2, probs
+
+
+def cls_loss_bwd(score2d, labels, weights, a_pos: float, a_neg: float, gamma: float, out2, grad_out):
+    """d loss / d score2d in score2d's dtype (dl_cls_loss_bwd); out2 from cls_loss_fwd, grad_out a device fp32 scalar."""
+    N, ld = _cls_loss_operands(score2d, labels, weights, "cls_loss_bwd")
+    d = torch.empty((N, score2d.shape[1]), dtype=score2d.dtype, device=score2d.device)
+    check(_lib.lib().dl_cls_loss_bwd(score2d.data_ptr(), ld, score2d.shape[1], _dt(score2d), labels.data_ptr(), _ptr(weights), N,
+                                     float(a_pos), float(a_neg), float(gamma), out2.data_ptr(), grad_out.data_ptr(), d.data_ptr(),
+                                     score2d.shape[1], _stream()), "dl_cls_loss_bwd")
+    return d
+
+
 def gate_dpre(dl2d, w2, pre2d):
     """dpre = gelu'(pre) o (dl @ w2): dl (M, 8), w2 (8, d_diff), pre (M, d_diff), all in one compute dtype (dl_gate_dpre)."""
     _need_gpu(dl2d, w2, pre2d)
@@ -1326,14 +1367,52 @@ def guard_text(bits: int) -> str:
     return "; ".join(v for k, v in FLAG_TEXT.items() if bits & k) or "unknown flag bits %#x" % bits
 
 
+# The classification loss's own word (dl_cls_loss_fwd ORs FLAG_CLS_LABEL into it): the word above is the padding guards', and a
+# bad label is no padding fault.  One int32 per device, created by the first cls_loss_fwd on it: without the loss it does not
+# exist and nothing reads it.  check_guard_flags and the trainer's polling report both words.
+FLAG_CLS_LABEL = 1
+CLS_FLAG_TEXT = {FLAG_CLS_LABEL: "FLAG_CLS_LABEL: a label of the classification loss is outside [0, 1] or not finite, or a sample weight "
+                                 "(meta 'Weight') is negative or not finite; that sample's loss and gradient are NaN (dl_cls_loss_fwd)"}
+_cls_flags = {}
+
+
+def _dev_key(device):
+    dev = torch.device(device)
+    return dev, (dev.type, dev.index if dev.index is not None else (torch.cuda.current_device() if dev.type == "cuda" else 0))
+
+
+def cls_loss_flags(device, create: bool = True) -> Optional[torch.Tensor]:
+    """The classification loss's guard word of `device` (create=False: None while no cls_loss_fwd has run there)."""
+    dev, key = _dev_key(device)
+    t = _cls_flags.get(key)
+    if t is None and create:
+        t = _cls_flags[key] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return t
+
+
+def guard_message(bits: int, cls_bits: int = 0, when: str = "") -> str:
+    """The error text of tripped guard words (when: e.g. " in an earlier step")."""
+    parts = []
+    if bits:
+        parts.append("padding guard tripped%s — %s" % (when, guard_text(bits)))
+    if cls_bits:
+        parts.append("classification loss guard tripped%s — %s"
+                     % (when, "; ".join(v for k, v in CLS_FLAG_TEXT.items() if cls_bits & k) or "unknown flag bits %#x" % cls_bits))
+    return "druglamp_amd: " + "; ".join(parts)
+
+
 def check_guard_flags(device) -> None:
-    """Synchronising check of the device guard word: raises (and clears the word) when a compact padding form ran on a batch
-    that does not have the structure it assumes."""
+    """Synchronising check of the device guard words: raises (and clears them) when a compact padding form ran on a batch
+    that does not have the structure it assumes, or the classification loss met a bad label or sample weight."""
     t = guard_flags(device)
     bits = int(t.item())
-    if bits:
+    c = cls_loss_flags(device, create=False)
+    cls_bits = int(c.item()) if c is not None else 0
+    if bits or cls_bits:
         t.zero_()
-        raise RuntimeError("druglamp_amd: padding guard tripped — " + guard_text(bits))
+        if c is not None:
+            c.zero_()
+        raise RuntimeError(guard_message(bits, cls_bits))
 
 
 def embed_rows(ids: torch.Tensor, weight: torch.Tensor, fill: torch.Tensor, src: torch.Tensor, period: Optional[torch.Tensor]) -> torch.Tensor:

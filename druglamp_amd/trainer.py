@@ -23,12 +23,15 @@ What is new (MI355X-native):
   * optional gradient guard (Trainer(max_grad_norm=..., skip_nonfinite=...)): global-norm clipping and the skip of a step with
     a non-finite gradient, decided on the device from one fp64 pass over the flat gradient — no host round trip;
   * optional weight EMA (Trainer(ema_decay=...), WeightEMA): an averaged copy of the arena, one dl_ema_update pass per step behind
-    the last optimiser, swapped in for evaluation and screening (Trainer.ema_weights) or for good (Trainer.adopt_ema).
+    the last optimiser, swapped in for evaluation and screening (Trainer.ema_weights) or for good (Trainer.adopt_ema);
+  * optional imbalance-aware classification loss (Trainer(cls_loss=ClsLoss(...)), cls_loss.py): pos_weight, per-sample weights
+    (meta "Weight") and the focal term as one dl_cls_loss_fwd / dl_cls_loss_bwd launch pair in place of the torch loss tail.
 """
 from __future__ import annotations
 
 import collections
 import contextlib
+import dataclasses
 import math
 import os
 from typing import Dict, List, Optional, Sequence
@@ -38,6 +41,7 @@ import torch.distributed as dist
 
 from . import functional as Fn
 from . import ops
+from .cls_loss import ClsLoss, classification_loss, meta_weights
 from .model.basic_model import binary_cross_entropy, cross_entropy_logits
 
 # Trainer.hit_profiles: key_mass (P, k, cols) fp32, site_peak (P, k, n_site) fp32, site_key (P, k, n_site) int32, on the CPU
@@ -314,6 +318,10 @@ class GraphedStep:
         self.base = None                                        # (set by the trainer: kind + batch signature + by-value scalars)
         self.byval = ()
         self.labels = None
+        # Trainer(cls_loss=...) with per-sample weights (meta "Weight"): this graph's static weight tensor, refilled in run()
+        # beside the labels; whether there are weights is part of the trainer's graph key
+        w = meta_weights(meta) if trainer.cls_loss is not None else None
+        self.weights = None if w is None else w.to(dev)
         if "cm" in kind:
             from .model.cross_modality import CMCodes, CMLabels
             if trainer.model.cm_model.global_batch and trainer.world > 1:
@@ -357,7 +365,9 @@ class GraphedStep:
             ts += [self.labels.buf if hasattr(self.labels, "buf") else self.labels.dev]
         if self.hints.protein_plan is not None:
             ts += [self.hints.protein_plan.buf]
-        ts += list(ops._guard_flags.values())
+        if self.weights is not None:
+            ts += [self.weights]
+        ts += list(ops._guard_flags.values()) + list(ops._cls_flags.values())
         ts += list(ops._seed_offsets.values()) + list(ops._tickets.values())
         ts += [e.image for e in Fn._lowp_cache.values() if torch.is_tensor(e.image)]
         for tab in list(Fn._lowp_tables.values()) + [t for t in Fn._lowp_retired if isinstance(t, tuple) and len(t) == 4]:
@@ -412,7 +422,10 @@ class GraphedStep:
         # (hints: by-value knowledge of the capture — the block sizes are part of the graph key, the table CONTENTS are refilled)
         _, _, ssl_input, cm_input, score = m(feat_d, feat_p, llm_d, llm_p, hints=self.hints)
         tr._zero_grad()
-        _, cls_loss = binary_cross_entropy(score, labels) if tr.n_class == 1 else cross_entropy_logits(score, labels)
+        if tr.cls_loss is not None:
+            _, cls_loss = classification_loss(score, labels, tr.cls_loss, self.weights)
+        else:
+            _, cls_loss = binary_cross_entropy(score, labels) if tr.n_class == 1 else cross_entropy_logits(score, labels)
         out = {"cls": cls_loss.detach()}
         if "ssl" in self.kind:
             with m._glue(), Fn.deferred_bn_ticks():     # (the heads' BatchNorm step counters advance in one launch)
@@ -448,7 +461,8 @@ class GraphedStep:
         """The backward pass the optimisers consume (the key of the agreed gradient set)."""
         return "cm" if "cm" in self.kind else self.kind
 
-    def run(self, batch, meta=None):
+    def run(self, batch, meta=None, weights=None):
+        """weights: this step's meta_weights(meta), where the trainer has them already."""
         if self.hints.protein_plan is not None:    # this batch's residue counts -> the graph's static tables (built on the device)
             spec = self.tr.protein_plan_of(meta, batch, must_pay=False)
             if spec is None or spec.need > self.hints.protein_plan.rows:
@@ -459,6 +473,11 @@ class GraphedStep:
                 self.labels.fill(meta, self.tr.model.cm_model.use_cm)
             else:
                 self.labels.fill(meta)
+        if self.weights is not None:               # this step's sample weights -> the graph's static weight tensor
+            w = weights if weights is not None else meta_weights(meta)
+            if w is None or w.numel() != self.weights.numel():
+                raise RuntimeError("GraphedStep: the graph was captured with per-sample weights; this step's meta has none for the batch")
+            self.weights.copy_(w)
         if not self._is_static(batch):                  # copy into the static inputs (device-to-device)
             for dst, src in zip(self.static, batch):
                 if isinstance(dst, tuple):
@@ -490,12 +509,13 @@ class Trainer:
     grad_bf16 = False
     graph_allreduce = False
     ema = None
+    cls_loss = None
     _ema_spare = None
     _ema_swapped = False
 
     def __init__(self, model, cfg, device=None, compute_dtype=torch.float32, graph_steps: bool = False, freeze_bn: bool = False,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_decay: Optional[float] = None,
-                 ema_warmup: bool = False):
+                 ema_warmup: bool = False, cls_loss: Optional[ClsLoss] = None):
         """freeze_bn=True: fine-tuning with frozen BatchNorm (model.freeze_batchnorm()): every BatchNorm1d normalises with its
         running statistics, which the steps leave bitwise unchanged; its weight / bias train.  cls steps only (eager or
         replayed): with the SSL or the CM head switched on (RS.SSL / RS.CM) construction raises.
@@ -523,7 +543,26 @@ class Trainer:
         per-parameter step counts above, `ema.updates` advances on a skipped step all the same, and with ema_warmup the
         weight schedule counts it.  The shadow is a function of bit-identical parameters and a bit-identical guard decision
         on every rank: replicas hold the same shadow without another collective.  ema_weights() / adopt_ema() put the
-        average to use; fit() validates and selects on it.  Buffers (BatchNorm running statistics) are shared, not averaged."""
+        average to use; fit() validates and selects on it.  Buffers (BatchNorm running statistics) are shared, not averaged.
+
+        cls_loss: the imbalance-aware classification loss (cls_loss.ClsLoss: pos_weight / neg_weight / focal gamma; off unless
+        given: a step then calls what it calls without it and nothing is allocated).  On, the eager step and the captured
+        body take the step's classification loss from cls_loss.classification_loss (one dl_cls_loss_fwd and one
+        dl_cls_loss_bwd launch at the step's batch sizes, for one- and two-output classifiers alike); everything behind the
+        loss — gradient guard, optimisers, EMA, all-reduce — is untouched.  Per-sample weights arrive through meta: when
+        every entry of a step's meta has a "Weight" key, the step weights its samples with them (a (B,) fp32 device tensor;
+        a captured step refills its own static copy before every replay, and whether a step has weights is part of the graph
+        key); weights on only some entries raise ValueError.  The weights are a Python list turned into B floats and copied
+        from pageable host memory, so a step WITH weights waits for that small copy; a step without them never synchronises.
+        A negative or non-finite weight, like a label outside [0, 1], makes the loss and that sample's gradient NaN and raises
+        FLAG_CLS_LABEL in the loss's own device guard word, which the step's polling and check_device_flags report beside the
+        padding guards (with skip_nonfinite such a step is skipped, not silent).  predict / evaluate keep reporting the
+        unweighted loss, so validation losses stay comparable across settings; fit is unchanged.  At world > 1 the loss and
+        its normaliser (the batch size, or the sum of the weights) are rank-local, like every other mean of the step: the
+        all-reduce averages the ranks' gradients of their own normalised losses."""
+        if cls_loss is not None and not isinstance(cls_loss, ClsLoss):
+            raise ValueError("Trainer(cls_loss=%r): must be None or a ClsLoss" % (cls_loss,))
+        self.cls_loss = cls_loss
         if ema_decay is not None:
             ok = isinstance(ema_decay, (int, float)) and not isinstance(ema_decay, bool) and 0.0 <= float(ema_decay) < 1.0
             if not ok:
@@ -634,6 +673,10 @@ class Trainer:
         on_gpu = torch.device(self.device).type == "cuda"
         self._guard_pin = torch.zeros(1, dtype=torch.int32).pin_memory() if on_gpu else None
         self._guard_event = None
+        # (the classification loss's own guard word and its pinned copy exist only with cls_loss: created here, before any capture)
+        self._cls_pin = torch.zeros(1, dtype=torch.int32).pin_memory() if (on_gpu and cls_loss is not None) else None
+        if self._cls_pin is not None:
+            ops.cls_loss_flags(self.device)
         if self.graph_steps:
             ops.use_seed_offset(True)    # one dropout-seed regime for eager and replayed steps
 
@@ -808,15 +851,20 @@ class Trainer:
         ev = self._guard_event
         if ev is not None and ev.query():
             bits = int(self._guard_pin[0])
+            cls_bits = int(self._cls_pin[0]) if self._cls_pin is not None else 0
             self._guard_event = None
-            if bits:
+            if bits or cls_bits:
                 ops.guard_flags(self.device).zero_()
-                raise RuntimeError("druglamp_amd: padding guard tripped in an earlier step — " + ops.guard_text(bits))
+                if cls_bits:
+                    ops.cls_loss_flags(self.device).zero_()
+                raise RuntimeError(ops.guard_message(bits, cls_bits, " in an earlier step"))
 
     def _post_guard(self):
         if self._guard_pin is None or self._guard_event is not None:
             return                                        # one copy in flight at a time (the word is sticky)
         self._guard_pin.copy_(ops.guard_flags(self.device), non_blocking=True)
+        if self._cls_pin is not None:
+            self._cls_pin.copy_(ops.cls_loss_flags(self.device), non_blocking=True)
         self._guard_event = torch.cuda.Event()
         self._guard_event.record()
 
@@ -848,6 +896,11 @@ class Trainer:
         if self._ema_swapped:
             raise RuntimeError("Trainer.training_step inside ema_weights(): the arena holds the averaged weights")
         self._poll_guard()
+        w_host = None
+        if self.cls_loss is not None:
+            w_host = meta_weights(meta)          # (raises when only some entries carry a "Weight")
+            if w_host is not None and w_host.numel() != int(batch[2].shape[0]):
+                raise ValueError("Trainer.training_step: meta holds %d weights for a batch of %d" % (w_host.numel(), int(batch[2].shape[0])))
         if not m.training:
             m.train()                  # (walks every submodule: 0.7 ms per call)
         compute_ssl = self.use_ssl and (cur_epoch % self.ssl_epoch_step == 0)
@@ -868,13 +921,15 @@ class Trainer:
             byval = (float(m.cm_model.m_sch_loss_fn.margin), float(self.cm_weight)) if compute_cm else ()
             # (frozen BatchNorm is by-value knowledge of a capture too: such a graph has no statistics launches)
             base = (kind,) + (("frozen_bn",) if getattr(m, "bn_frozen", False) else ()) + GraphedStep.signature(batch) + byval
+            if self.cls_loss is not None:            # (the loss's constants are by-value arguments of a capture; with / without weights: another body)
+                base += (("cls_loss", dataclasses.astuple(self.cls_loss), w_host is not None),)
             # (must_pay=False for the LOOKUP: a batch whose compact layout would not pay on its own still fits — and replays —
             #  a graph that holds tables of its size; GraphedStep.run builds its spec the same way)
             spec_any = self.protein_plan_of(meta, batch, must_pay=False)
             blk = self.padding_hints_of(meta, batch).get("drug_tokens", 0)
             g = self._find_graph(base, blk, spec_any)
             if g is not None:
-                return self._graphed_step(g, batch, meta)
+                return self._graphed_step(g, batch, meta, w_host)
             spec = spec_any if (spec_any is not None and spec_any.pays()) else None
             # No captured graph serves this batch.  Capacities of the next capture: size CLASSES (row_class: a geometric
             # ladder; drug-token blocks of 128), never below what an earlier batch of this shape asked for — so the captures
@@ -884,7 +939,7 @@ class Trainer:
             eager_caps = self._capture_caps(base, blk, spec)
             key = base + eager_caps
             if self._eager_seen.get(key, 0) >= self.graph_warmup:
-                return self._graphed_step(self._capture(key, base, byval, batch, kind, meta, eager_caps), batch, meta)
+                return self._graphed_step(self._capture(key, base, byval, batch, kind, meta, eager_caps), batch, meta, w_host)
             if len(self._eager_seen) > 256:            # bounded bookkeeping (signatures of shapes seen once and never again)
                 self._eager_seen.clear()
             self._eager_seen[key] = self._eager_seen.get(key, 0) + 1
@@ -892,7 +947,10 @@ class Trainer:
         kind_now = "cm" if compute_cm else "ssl" if compute_ssl else "cls"
         _, _, ssl_input, cm_input, score = m(feat_d, feat_p, llm_d, llm_p, hints=self.hints_of(meta, batch, kind=kind_now, caps=eager_caps))
         self._zero_grad()
-        _, cls_loss = binary_cross_entropy(score, labels) if self.n_class == 1 else cross_entropy_logits(score, labels)
+        if self.cls_loss is not None:
+            _, cls_loss = classification_loss(score, labels, self.cls_loss, None if w_host is None else w_host.to(self.device))
+        else:
+            _, cls_loss = binary_cross_entropy(score, labels) if self.n_class == 1 else cross_entropy_logits(score, labels)
         last = "cm" if compute_cm else "ssl" if compute_ssl else "cls"     # the backward the optimisers consume
         if last == "cls" or self.run_dead_backward:
             self._arm(last, "cls")
@@ -1073,10 +1131,10 @@ class Trainer:
         self.graph_captures += 1
         return g
 
-    def _graphed_step(self, g: "GraphedStep", batch, meta=None) -> Dict[str, float]:
+    def _graphed_step(self, g: "GraphedStep", batch, meta=None, weights=None) -> Dict[str, float]:
         kind = g.kind
         self._graphs[g.key] = self._graphs.pop(g.key)                        # most recently used last
-        out, idx = g.run(batch, meta)
+        out, idx = g.run(batch, meta, weights)
         if self.world > 1 and not g.reduced:
             idx = self._agreed(g.last, idx)
             self._all_reduce_runs(idx)

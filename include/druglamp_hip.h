@@ -814,6 +814,33 @@ int dl_ce_rows_fwd(const void* logits, int64_t ld, const int64_t* labels, int64_
                    float* lse, float* out2, void* workspace, size_t workspace_bytes, dl_stream s);
 int dl_ce_rows_bwd(const void* logits, int64_t ld, const int64_t* labels, int64_t N, int32_t C, int64_t ignore_index, int32_t dtype,
                    const float* lse, const float* out2, const float* grad_out, void* dlogits, int64_t ldd, int32_t Cp, dl_stream s);
+/* Imbalance-aware classification loss (cls_loss.hip): weighted / focal binary cross entropy on the classifier's logits.
+ * score [N][ld] (fp32 / bf16, ld >= n_out), labels fp32 [N] in [0, 1], weights fp32 [N] or NULL (every weight 1).  Row i:
+ *   z = score[i][0] (n_out == 1) or score[i][1] - score[i][0] (n_out == 2),  p = sigmoid(z),  y = labels[i],  w = weights[i],
+ *   d = |y sigmoid(-z) - (1 - y) sigmoid(z)| (= |y - p|, without cancellation in the tails),  m = d^gamma (gamma == 0: 1),
+ *   l = w m [a_pos y softplus(-z) + a_neg (1 - y) softplus(z)],   softplus(t) = max(t, 0) + log1p(exp(-|t|)).
+ * fwd: probs[i] = p (probs may be NULL), out2[0] = sum_i l / den, out2[1] = den; den = N without weights, the sum of the valid
+ * weights with (den == 0: NaN, 0 / 0).  bwd: dscore [N][ldd] in score's dtype, g = grad_out[0] / out2[1] * d l / d z in the one
+ * column, (-g, +g) in two; the full derivative, d m / d z = -gamma d^(gamma - 1) sgn(y - p) p (1 - p) with sgn(0) = 0; recomputed
+ * from z, nothing is saved per row; grad_out is a DEVICE scalar and out2 the forward's.  Columns >= n_out are not written.
+ * a_pos, a_neg finite, >= 0, not both 0; gamma == 0 or 1 <= gamma <= 8 (else DL_ERR_ARG).  a_pos = pw, a_neg = 1, gamma = 0 is
+ * BCE-with-logits with pos_weight pw; a_pos = alpha, a_neg = 1 - alpha is the focal loss; (1, 1, 0) on two outputs is the
+ * two-class cross entropy.
+ * Forms: N <= 4096 rows — one 256-thread workgroup does rows, sum and division in ONE launch and needs no workspace
+ * (dl_cls_loss_workspace_bytes returns 0, workspace may be NULL); above, one row per thread with a pair of partial sums per
+ * 256 rows in the workspace and a final one-workgroup launch.  The backward is one launch.  Fixed summation order, no
+ * floating-point atomics: bitwise repeatable.
+ * Bad inputs: a non-finite z makes that row's loss term and gradient NaN (so the loss is NaN; probs is sigmoid(z) by IEEE
+ * rules: 1, 0, NaN for +inf, -inf, NaN); a label outside [0, 1] or not finite, or a weight that is negative or not finite,
+ * poisons its row the same way and ORs `code` into *flags (a caller-owned word, as for dl_rows_equal_check; flags may be NULL).
+ * A bad weight counts 0 in den, so the other rows keep their gradient. */
+size_t dl_cls_loss_workspace_bytes(int64_t N);
+int dl_cls_loss_fwd(const void* score, int64_t ld, int32_t n_out, int32_t dtype, const float* labels, const float* weights, int64_t N,
+                    float a_pos, float a_neg, float gamma, float* probs, float* out2, void* workspace, size_t workspace_bytes,
+                    uint32_t code, uint32_t* flags, dl_stream s);
+int dl_cls_loss_bwd(const void* score, int64_t ld, int32_t n_out, int32_t dtype, const float* labels, const float* weights, int64_t N,
+                    float a_pos, float a_neg, float gamma, const float* out2, const float* grad_out, void* dscore, int64_t ldd,
+                    dl_stream s);
 /* General form (round 3): the rows whose loss / gradient a call produces (side `a`, resident) are scored against a second
  * set of rows (side `b`, streamed); each side is [q rows ; k rows], n rows per half, row-major (n x d), dtype DL_F32 or
  * DL_BF16 (bf16 operands on v_mfma_f32_16x16x32_bf16, log-sum-exp / loss / gradients in fp32).  Rows are identified
