@@ -310,6 +310,8 @@ SIGNATURES = {
     "dl_grad_guard_finalize": (c_i32, [c_vp, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp]),
     "dl_adamw_step_guarded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_f32, c_vp,
                                       c_i32, c_vp, c_vp]),
+    "dl_adamw_step_groups": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_i64, c_f32, c_vp, c_i32,
+                                     c_vp, c_vp, c_i32, c_vp, c_vp]),
     "dl_ema_update": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "dl_bn_stats_rw": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp, c_sz, c_vp]),
     "dl_bn_apply_fwd_rw": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_vp]),

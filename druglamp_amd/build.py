@@ -81,8 +81,11 @@ def _stale(out, deps):
 # the same bits.
 # ema.hip gets the flag: per-element fp32 on 16-byte vectors, HBM-bound (the packed forms buy nothing) — bn_eval.hip's caution.
 # cls_loss.hip gets the flag: per-element fp32 on a few hundred rows (the packed forms buy nothing) — the same caution.
+# adamw_groups.hip gets the flag: its kernel is elementwise.hip's AdamW arithmetic (csrc/adamw.cuh) with per-chunk lr and decay,
+# and it must give dl_adamw_step's bits segment by segment — grad_guard.hip's reason.
 FILE_FLAGS = {"norm.hip": ["-fno-slp-vectorize"], "elementwise.hip": ["-fno-slp-vectorize"], "bn_eval.hip": ["-fno-slp-vectorize"],
-              "grad_guard.hip": ["-fno-slp-vectorize"], "ema.hip": ["-fno-slp-vectorize"], "cls_loss.hip": ["-fno-slp-vectorize"]}
+              "grad_guard.hip": ["-fno-slp-vectorize"], "ema.hip": ["-fno-slp-vectorize"], "cls_loss.hip": ["-fno-slp-vectorize"],
+              "adamw_groups.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src, force, objdir=OBJDIR, extra=()):

@@ -902,6 +902,29 @@ def adamw_step_guarded(param, grad, exp_avg, exp_avg_sq, guard, *, lr, beta1=0.9
                                            guard.data_ptr(), _stream()), "dl_adamw_step_guarded")
 
 
+def adamw_step_groups(param, grad, exp_avg, exp_avg_sq, quad_group, group_tab, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, step,
+                      grad_scale=1.0, lowp=None, guard=None):
+    """adamw_step (guard None) / adamw_step_guarded with a learning-rate scale and a weight decay per group (csrc/adamw_groups.hip):
+    quad_group, uint8, one id per 16-byte chunk of param (ceil(n / 4) entries); group_tab, fp32 (n_groups, 2) rows
+    {lr_scale, weight_decay}.  A maximal segment of equal id gets the bits of adamw_step[_guarded] on that segment alone with
+    lr = float32(lr) * float32(lr_scale) and that decay; a chunk whose id has no row is not touched."""
+    n = param.numel()
+    _need_gpu(param, grad, exp_avg, exp_avg_sq, quad_group, group_tab, guard)
+    if quad_group.dtype != torch.uint8 or not quad_group.is_contiguous() or quad_group.numel() != (n + 3) // 4:
+        raise ValueError("adamw_step_groups: quad_group must be a contiguous uint8 tensor of ceil(n / 4) = %d entries (got %s, %d)"
+                         % ((n + 3) // 4, quad_group.dtype, quad_group.numel()))
+    if group_tab.dtype != torch.float32 or not group_tab.is_contiguous() or group_tab.dim() != 2 or group_tab.shape[1] != 2:
+        raise ValueError("adamw_step_groups: group_tab must be a contiguous float32 (n_groups, 2) tensor (got %s, %s)"
+                         % (group_tab.dtype, tuple(group_tab.shape)))
+    if guard is not None and (guard.dtype != torch.float32 or guard.numel() < 4):
+        raise ValueError("adamw_step_groups: guard must hold 4 float32 values")
+    check(_lib.lib().dl_adamw_step_groups(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
+                                          float(lr), float(beta1), float(beta2), float(eps), int(step), float(grad_scale),
+                                          _ptr(lowp), _DT[lowp.dtype] if lowp is not None else 0, quad_group.data_ptr(),
+                                          group_tab.data_ptr(), int(group_tab.shape[0]), _ptr(guard), _stream()),
+          "dl_adamw_step_groups")
+
+
 class GradGuard:
     """The device state of one trainer's gradient guard: the fp64 sum, the partials workspace (sized once for `numel`
     elements: it serves any run of at most that many), guard = {coefficient, norm, skip flag, 0} and the cumulative

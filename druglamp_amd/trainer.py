@@ -25,7 +25,10 @@ What is new (MI355X-native):
   * optional weight EMA (Trainer(ema_decay=...), WeightEMA): an averaged copy of the arena, one dl_ema_update pass per step behind
     the last optimiser, swapped in for evaluation and screening (Trainer.ema_weights) or for good (Trainer.adopt_ema);
   * optional imbalance-aware classification loss (Trainer(cls_loss=ClsLoss(...)), cls_loss.py): pos_weight, per-sample weights
-    (meta "Weight") and the focal term as one dl_cls_loss_fwd / dl_cls_loss_bwd launch pair in place of the torch loss tail.
+    (meta "Weight") and the focal term as one dl_cls_loss_fwd / dl_cls_loss_bwd launch pair in place of the torch loss tail;
+  * optional parameter groups (Trainer(param_groups=[ParamGroup(...)]), param_groups.py): a learning-rate scale and a weight decay
+    per group and frozen parts, with the group looked up per 16-byte chunk inside the optimiser kernel (dl_adamw_step_groups) —
+    the launches per optimiser stay the one to three of its runs.
 """
 from __future__ import annotations
 
@@ -42,6 +45,7 @@ import torch.distributed as dist
 from . import functional as Fn
 from . import ops
 from .cls_loss import ClsLoss, classification_loss, meta_weights
+from .param_groups import ParamGroup, ParamGroups
 from .model.basic_model import binary_cross_entropy, cross_entropy_logits
 
 # Trainer.hit_profiles: key_mass (P, k, cols) fp32, site_peak (P, k, n_site) fp32, site_key (P, k, n_site) int32, on the CPU
@@ -225,19 +229,31 @@ class GradOverlap:
 
 
 class FusedAdamW:
-    """torch.optim.AdamW semantics (lr, betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2) on a FlatParams."""
+    """torch.optim.AdamW semantics (lr, betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2) on a FlatParams.
+    groups (a built param_groups.ParamGroups, or None): every run is ONE dl_adamw_step_groups launch in place of the
+    dl_adamw_step / dl_adamw_step_guarded one — the runs are still formed by step counts alone; the kernel resolves the group
+    of each 16-byte chunk from groups.quad_group[s / 4 : e / 4] and multiplies this optimiser's lr by the group's scale."""
+    WEIGHT_DECAY = 1e-2
 
-    def __init__(self, flat: FlatParams, lr: float, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, flat: FlatParams, lr: float, betas=(0.9, 0.999), eps=1e-8, weight_decay=WEIGHT_DECAY, groups=None):
         self.flat, self.lr, self.betas, self.eps, self.wd = flat, lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat.arena)
         self.exp_avg_sq = torch.zeros_like(flat.arena)
         self.steps = [0] * len(flat.params)
+        self.groups = groups
 
     def step(self, idx: List[int], grad_scale: float = 1.0, guard: Optional[torch.Tensor] = None):
         """guard (ops.GradGuard.guard, a device tensor): the guarded kernel scales the gradient by grad_scale * guard[0] and
         writes nothing when guard[2] != 0.  The per-parameter step counts advance either way: the host does not know the
         device's decision."""
+        gr = self.groups
         for s, e, first in self.flat.runs(idx, lambda i: self.steps[i]):
+            if gr is not None:
+                ops.adamw_step_groups(self.flat.arena[s:e], self.flat.grads[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e],
+                                      gr.quad_group[s // 4:e // 4], gr.group_tab, lr=self.lr, beta1=self.betas[0],
+                                      beta2=self.betas[1], eps=self.eps, step=self.steps[first] + 1, grad_scale=grad_scale,
+                                      guard=guard)
+                continue
             kw = dict(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
                       step=self.steps[first] + 1, grad_scale=grad_scale)
             if guard is None:
@@ -510,15 +526,32 @@ class Trainer:
     graph_allreduce = False
     ema = None
     cls_loss = None
+    param_groups = None
     _ema_spare = None
     _ema_swapped = False
 
     def __init__(self, model, cfg, device=None, compute_dtype=torch.float32, graph_steps: bool = False, freeze_bn: bool = False,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_decay: Optional[float] = None,
-                 ema_warmup: bool = False, cls_loss: Optional[ClsLoss] = None):
+                 ema_warmup: bool = False, cls_loss: Optional[ClsLoss] = None, param_groups: Optional[Sequence[ParamGroup]] = None):
         """freeze_bn=True: fine-tuning with frozen BatchNorm (model.freeze_batchnorm()): every BatchNorm1d normalises with its
         running statistics, which the steps leave bitwise unchanged; its weight / bias train.  cls steps only (eager or
         replayed): with the SSL or the CM head switched on (RS.SSL / RS.CM) construction raises.
+
+        param_groups: a sequence of param_groups.ParamGroup (None or empty: off — nothing is allocated and a step calls exactly
+        what it calls without them).  On, every parameter belongs to the first group that selects it (fnmatch patterns over
+        model.named_parameters() names, or max_ndim; the rest is group "default": scale 1, the optimiser's weight decay), and
+        every optimiser launch of a step is a dl_adamw_step_groups launch over the same run, eager and replayed steps alike
+        (the optimisers run outside the captured graph): the group of each 16-byte chunk is read on the device from ONE chunk
+        table that opt, opt_ssl and opt_cm share, each multiplies its own scheduled lr by the group's lr_scale (one fp32
+        multiply) and uses the group's weight_decay.  The launch count of a step does not change.  set_param_group rewrites a
+        group's values between steps; param_group_table lists the assignment.
+        A group with frozen=True: requires_grad is switched off for its parameters first thing here, before the arena, the
+        overlap hooks and any capture exist.  The parameters stay in the arena (the EMA, checkpoints and sync_replicas see
+        them) but never receive a gradient, so they are in no optimiser run, not in the gradient guard's norm and not in the
+        all-reduce; their arena values, both moments and their EMA shadow keep their bits.
+          * BatchNorm running statistics are buffers, not parameters: a frozen module's BatchNorm still updates them in
+            training mode unless freeze_bn is on as well.
+          * lr_scale=0 is NOT freezing: the moments still move, and a -0.0 parameter can become +0.0.
 
         max_grad_norm / skip_nonfinite: the gradient guard (off unless one of them is set; off = the launches of a step are
         exactly those without it and no state is allocated).  On, every step — eager or replayed — measures the global L2 norm
@@ -562,6 +595,9 @@ class Trainer:
         all-reduce averages the ranks' gradients of their own normalised losses."""
         if cls_loss is not None and not isinstance(cls_loss, ClsLoss):
             raise ValueError("Trainer(cls_loss=%r): must be None or a ClsLoss" % (cls_loss,))
+        if param_groups:         # (first thing: frozen parameters lose requires_grad before FlatParams, GradOverlap and any capture)
+            self.param_groups = ParamGroups(model, param_groups, default_weight_decay=FusedAdamW.WEIGHT_DECAY)
+            self.param_groups.freeze()
         self.cls_loss = cls_loss
         if ema_decay is not None:
             ok = isinstance(ema_decay, (int, float)) and not isinstance(ema_decay, bool) and 0.0 <= float(ema_decay) < 1.0
@@ -601,9 +637,10 @@ class Trainer:
             self.sync_replicas()
         Fn.bump_param_epoch()
         warm = int(self.epochs * 0.2)
-        self.opt = FusedAdamW(self.flat, cfg["SOLVER"]["LR"])
-        self.opt_ssl = FusedAdamW(self.flat, cfg["SOLVER"]["SSL_LR"]) if self.use_ssl else None
-        self.opt_cm = FusedAdamW(self.flat, cfg["SOLVER"]["CM_LR"]) if self.use_cm else None
+        pg = self.param_groups.build(self.flat) if self.param_groups is not None else None   # one table for the three optimisers
+        self.opt = FusedAdamW(self.flat, cfg["SOLVER"]["LR"], groups=pg)
+        self.opt_ssl = FusedAdamW(self.flat, cfg["SOLVER"]["SSL_LR"], groups=pg) if self.use_ssl else None
+        self.opt_cm = FusedAdamW(self.flat, cfg["SOLVER"]["CM_LR"], groups=pg) if self.use_cm else None
         self.grad_guard = None
         self._guard_runs = None
         if self.max_grad_norm is not None or self.skip_nonfinite:
@@ -1020,6 +1057,21 @@ class Trainer:
         g = self.grad_guard.guard.tolist()
         c = self.grad_guard.counters.tolist()
         return {"norm": g[1], "coef": g[0], "skipped": int(c[0]), "clipped": int(c[1])}
+
+    # -- parameter groups -------------------------------------------------------------------------------------------------
+    def set_param_group(self, name: str, lr_scale: Optional[float] = None, weight_decay: Optional[float] = None):
+        """New lr_scale and / or weight_decay for one group ("default" included), from the next step on: one row of the device
+        table is rewritten (a small copy between steps).  ValueError for an unknown name or a negative / non-finite value;
+        whether a group is frozen cannot change."""
+        if self.param_groups is None:
+            raise RuntimeError("Trainer.set_param_group: parameter groups are off (param_groups)")
+        self.param_groups.set(name, lr_scale=lr_scale, weight_decay=weight_decay)
+
+    def param_group_table(self) -> List[tuple]:
+        """[(group name, parameter name, numel)] in parameter order."""
+        if self.param_groups is None:
+            raise RuntimeError("Trainer.param_group_table: parameter groups are off (param_groups)")
+        return self.param_groups.table()
 
     # -- weight EMA -------------------------------------------------------------------------------------------------------
     @contextlib.contextmanager

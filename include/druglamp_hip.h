@@ -933,6 +933,33 @@ int dl_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float
                           float grad_scale, void* param_lowp, int32_t lowp_dtype, const float* guard, dl_stream s);
 
 /* ------------------------------------------------------------------------------------------
+ * Fused AdamW with parameter groups: a learning-rate scale and a weight decay per group, the group looked up on the device
+ * per 16-byte chunk, so that one launch serves a run of parameters of mixed groups.
+ *
+ * dl_adamw_step_groups: quad_group holds ceil(n / 4) bytes, quad_group[q] = the group id k of elements 4q .. 4q+3 (the flat
+ *   arena pads every parameter to a multiple of 4 elements: a chunk belongs to one parameter); group_tab holds n_groups rows
+ *   of 2 floats {lr_scale, weight_decay}.  The chunk is updated by dl_adamw_step's arithmetic (csrc/adamw.cuh, the single
+ *   definition) with lr_k = lr * group_tab[2k], ONE fp32 multiply, and weight_decay = group_tab[2k + 1].
+ *   Bit contract: for every maximal segment of equal group id, param, exp_avg, exp_avg_sq and param_lowp hold the bits of
+ *   dl_adamw_step (guard null) / dl_adamw_step_guarded (guard given) called on that segment alone with lr = (float)lr *
+ *   (float)lr_scale and that weight decay.
+ *   guard: null, or the 16-byte {coef, norm, skip, 0} record of dl_grad_guard_finalize: the gradient scale is
+ *   (float)(grad_scale * guard[0]), and when guard[2] != 0 nothing is written (one 16-byte load at a wave-uniform address,
+ *   return before any other access, as dl_adamw_step_guarded).
+ *   A chunk whose id is >= n_groups is not touched: its table row is not read and nothing of it is written (memory safety
+ *   against a bad table; druglamp_amd.param_groups never builds one).  lr_scale = 0 is NOT freezing: the moments move and
+ *   p * (1 - 0 * wd) - 0 * (m / denom) turns a -0.0 parameter into +0.0.
+ *   16-byte loads and stores with a scalar tail for n % 4; one 16-byte chunk per thread, the grid a function of n alone; no
+ *   atomics, no LDS: two calls on the same data agree bit for bit.  28.25 B per element (28 of AdamW + the id byte per chunk).
+ *   DL_ERR_ARG before anything is launched: null param / grad / exp_avg / exp_avg_sq / quad_group / group_tab, n <= 0,
+ *   step < 1, n_groups outside [1, 64], guard not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int dl_adamw_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                         float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
+                         void* param_lowp, int32_t lowp_dtype, const uint8_t* quad_group, const float* group_tab,
+                         int32_t n_groups, const float* guard, dl_stream s);
+
+/* ------------------------------------------------------------------------------------------
  * Weight EMA: a shadow copy of the flat parameter arena moved towards the live parameters, one pass per training step.
  *
  * dl_ema_update: for every i < n, in fp32,
