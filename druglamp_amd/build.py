@@ -77,15 +77,13 @@ def _stale(out, deps):
 # bn_eval.hip gets the flag: its 16-byte form is the unpack-then-fp32 pattern above, it is HBM-bound (the packed forms buy
 # nothing) and tests/test_contention_gpu.py does not cover it.  tests/test_bn_eval_bwd_gpu.py passes with the flag and, in an
 # A/B build (DL_BUILD_NOSLP_FILES=norm.hip,elementwise.hip), without it: the choice is caution, not a failing test.
-# grad_guard.hip gets the flag: its guarded AdamW kernel is elementwise.hip's arithmetic (csrc/adamw.cuh), and the two must give
-# the same bits.
-# ema.hip gets the flag: per-element fp32 on 16-byte vectors, HBM-bound (the packed forms buy nothing) — bn_eval.hip's caution.
+# optim.hip gets the flag: its AdamW arithmetic was compiled without the vectoriser when it lived in elementwise.hip, and the
+# EMA is per-element fp32 on 16-byte vectors, HBM-bound (the packed forms buy nothing) — bn_eval.hip's caution.  The plain, the
+# guarded and the grouped AdamW step are one kernel there, so their equal bits no longer rest on this table.
+# grad_guard.hip keeps the flag so that its sum-of-squares code is generated as it was while the file also held the guarded AdamW.
 # cls_loss.hip gets the flag: per-element fp32 on a few hundred rows (the packed forms buy nothing) — the same caution.
-# adamw_groups.hip gets the flag: its kernel is elementwise.hip's AdamW arithmetic (csrc/adamw.cuh) with per-chunk lr and decay,
-# and it must give dl_adamw_step's bits segment by segment — grad_guard.hip's reason.
 FILE_FLAGS = {"norm.hip": ["-fno-slp-vectorize"], "elementwise.hip": ["-fno-slp-vectorize"], "bn_eval.hip": ["-fno-slp-vectorize"],
-              "grad_guard.hip": ["-fno-slp-vectorize"], "ema.hip": ["-fno-slp-vectorize"], "cls_loss.hip": ["-fno-slp-vectorize"],
-              "adamw_groups.hip": ["-fno-slp-vectorize"]}
+              "grad_guard.hip": ["-fno-slp-vectorize"], "optim.hip": ["-fno-slp-vectorize"], "cls_loss.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src, force, objdir=OBJDIR, extra=()):

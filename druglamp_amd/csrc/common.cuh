@@ -61,6 +61,8 @@ template <> struct DTypeOf<float> { static constexpr int value = DL_F32; };
 template <> struct DTypeOf<bf16_t> { static constexpr int value = DL_BF16; };
 
 static inline size_t dl_dtype_size(int dt) { return dt == DL_BF16 ? 2 : 4; }
+// host-side argument check: p is a multiple of a (a power of two); a null pointer passes
+static inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // ---- scalar conversions ---------------------------------------------------------------
 __device__ __forceinline__ float to_f32(float x) { return x; }

@@ -1,8 +1,7 @@
 // elementwise.hip — HBM-bound helpers on the path: MHLA token gate, positional add + dropout,
-// dropout re-application, casts, positional-table gradient, fused AdamW.
+// dropout re-application, casts, positional-table gradient.
 #include <math.h>
 #include "common.cuh"
-#include "adamw.cuh"
 
 namespace {
 
@@ -630,16 +629,6 @@ __global__ __launch_bounds__(256) void rowmod_sum_kernel(const T* __restrict__ x
   }
 }
 
-// ---------------- AdamW --------------------------------------------------------------------------
-template <typename TL>
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-                             float bc1, float bc2_sqrt, float gscale, TL* __restrict__ lowp) {
-  const int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i4 >= n) return;
-  adamw_thread<TL>(p, g, m, v, n, i4, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, lowp);   // (adamw.cuh: shared with dl_adamw_step_guarded)
-}
-
 inline uint32_t nblk(int64_t n, int t = 256) { return (uint32_t)((n + t - 1) / t); }
 }  // namespace
 
@@ -1150,23 +1139,5 @@ extern "C" int dl_rowmod_sum(const void* x, float* out, int64_t M, int64_t D, in
     hipLaunchKernelGGL((rowmod_sum_kernel<float>), dim3(nblk(n4, 64)), dim3(256), 0, s, (const float*)x, out, M,
                        (int)D, L, accumulate);
   DL_CHECK_LAUNCH("dl_rowmod_sum");
-  return DL_OK;
-}
-
-extern "C" int dl_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                             float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
-                             float grad_scale, void* param_lowp, int32_t lowp_dtype, dl_stream stream) {
-  hipStream_t s = (hipStream_t)stream;
-  DL_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, DL_ERR_ARG, "dl_adamw_step: bad args");
-  float bc1, bc2s;
-  adamw_bias_corrections(beta1, beta2, step, &bc1, &bc2s);
-  const uint32_t blocks = nblk((n + 3) / 4);
-  if (param_lowp && lowp_dtype == DL_BF16)
-    hipLaunchKernelGGL((adamw_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq, n, lr,
-                       beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, (bf16_t*)param_lowp);
-  else
-    hipLaunchKernelGGL((adamw_kernel<float>), dim3(blocks), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq, n, lr,
-                       beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, (float*)param_lowp);
-  DL_CHECK_LAUNCH("dl_adamw_step");
   return DL_OK;
 }

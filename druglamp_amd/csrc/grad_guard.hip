@@ -1,10 +1,10 @@
 // grad_guard.hip — the gradient guard of the training step: global-norm clipping and the non-finite step skip, decided on the
-// device.  Three entry points (contract: include/druglamp_hip.h):
+// device.  Two entry points (contract: include/druglamp_hip.h):
 //   dl_grad_sqnorm          sum of squares of a flat fp32 gradient run, fp64 from the per-element square onward, fixed order
 //   dl_grad_guard_finalize  one thread: sum -> {clip coefficient, norm, skip flag} + the caller's cumulative counters
-//   dl_adamw_step_guarded   dl_adamw_step with grad_scale * guard[0]; writes nothing when guard[2] != 0
+// What consumes the guard record, dl_adamw_step_guarded / dl_adamw_step_groups / dl_ema_update, is optim.hip.
 // Nothing here uses an atomic: every sum has one association, so two calls on the same data agree bit for bit.
-#include "adamw.cuh"
+#include "common.cuh"
 
 namespace {
 
@@ -95,20 +95,6 @@ __global__ void guard_finalize_kernel(const double* __restrict__ acc, float pre_
   counters[1] += (coef < 1.0 && !skip) ? 1 : 0;
 }
 
-template <typename TL>
-__global__ void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                     float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-                                     float bc1, float bc2_sqrt, float gscale, TL* __restrict__ lowp,
-                                     const float* __restrict__ guard) {
-  const f32x4 gd = *reinterpret_cast<const f32x4*>(guard);              // one load at a wave-uniform address
-  if (gd[2] != 0.0f) return;                                            // skipped step: nothing is written
-  const int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i4 >= n) return;
-  adamw_thread<TL>(p, g, m, v, n, i4, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale * gd[0], lowp);
-}
-
-inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int dl_grad_sqnorm(const float* g, int64_t n, double* acc, int32_t accumulate, void* workspace,
@@ -137,25 +123,5 @@ extern "C" int dl_grad_guard_finalize(const double* acc, float pre_scale, float 
   hipLaunchKernelGGL(guard_finalize_kernel, dim3(1), dim3(64), 0, s, acc, pre_scale, max_norm, (int)skip_nonfinite, guard,
                      counters);
   DL_CHECK_LAUNCH("dl_grad_guard_finalize");
-  return DL_OK;
-}
-
-extern "C" int dl_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                                     float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
-                                     void* param_lowp, int32_t lowp_dtype, const float* guard, dl_stream stream) {
-  hipStream_t s = (hipStream_t)stream;
-  DL_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && guard, DL_ERR_ARG, "dl_adamw_step_guarded: null pointer");
-  DL_CHECK_ARG(n > 0 && step >= 1, DL_ERR_ARG, "dl_adamw_step_guarded: need n > 0 and step >= 1");
-  DL_CHECK_ARG(aligned_to(guard, 16), DL_ERR_ARG, "dl_adamw_step_guarded: guard must be 16-byte aligned");
-  float bc1, bc2s;
-  adamw_bias_corrections(beta1, beta2, step, &bc1, &bc2s);
-  const uint32_t blocks = (uint32_t)(((n + 3) / 4 + 255) / 256);
-  if (param_lowp && lowp_dtype == DL_BF16)
-    hipLaunchKernelGGL((adamw_guarded_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq, n, lr,
-                       beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, (bf16_t*)param_lowp, guard);
-  else
-    hipLaunchKernelGGL((adamw_guarded_kernel<float>), dim3(blocks), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq, n, lr,
-                       beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, (float*)param_lowp, guard);
-  DL_CHECK_LAUNCH("dl_adamw_step_guarded");
   return DL_OK;
 }

@@ -865,13 +865,55 @@ def token_gate_bwd(dout, v, gate, H: int, add_residual: bool):
     return dv, dlogits
 
 
+# ---- fused AdamW (csrc/optim.hip): the plain, the guarded and the grouped step are one kernel behind three entry points ----
+def _adamw(who, param, grad, exp_avg, exp_avg_sq, *, lr, beta1, beta2, eps, weight_decay=0.0, step, grad_scale, lowp,
+           guard=None, quad_group=None, group_tab=None):
+    """Validate the tensors (TypeError / ValueError before the library is called, nothing launched), then call the entry point
+    the optional operands select: dl_adamw_step_groups with a group table, dl_adamw_step_guarded with a guard alone,
+    dl_adamw_step with neither."""
+    n = param.numel()
+    _need_gpu(param, grad, exp_avg, exp_avg_sq, lowp, guard, quad_group, group_tab)
+    for name, t in (("param", param), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("lowp", lowp),
+                    ("guard", guard), ("quad_group", quad_group), ("group_tab", group_tab)):
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (who, name))
+        if t.device != param.device:
+            raise ValueError("%s: %s is on %s, param on %s" % (who, name, t.device, param.device))
+    for name, t in (("param", param), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("guard", guard)):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("%s: %s must be float32 (got %s)" % (who, name, t.dtype))
+    for name, t in (("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("lowp", lowp)):
+        if t is not None and t.numel() != n:
+            raise ValueError("%s: %s has %d elements, param %d" % (who, name, t.numel(), n))
+    if lowp is not None and lowp.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("%s: lowp must be float32 or bfloat16 (got %s)" % (who, lowp.dtype))
+    if guard is not None and guard.numel() < 4:
+        raise ValueError("%s: guard must hold 4 floats (got %d)" % (who, guard.numel()))
+    lead = (param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n, float(lr), float(beta1), float(beta2),
+            float(eps))
+    tail = (int(step), float(grad_scale), _ptr(lowp), _DT[lowp.dtype] if lowp is not None else 0)
+    if group_tab is not None:
+        if quad_group.dtype != torch.uint8 or quad_group.numel() != (n + 3) // 4:
+            raise ValueError("%s: quad_group must be a contiguous uint8 tensor of ceil(n / 4) = %d entries (got %s, %d)"
+                             % (who, (n + 3) // 4, quad_group.dtype, quad_group.numel()))
+        if group_tab.dtype != torch.float32 or group_tab.dim() != 2 or group_tab.shape[1] != 2:
+            raise ValueError("%s: group_tab must be a contiguous float32 (n_groups, 2) tensor (got %s, %s)"
+                             % (who, group_tab.dtype, tuple(group_tab.shape)))
+        rc = _lib.lib().dl_adamw_step_groups(*lead, *tail, quad_group.data_ptr(), group_tab.data_ptr(), int(group_tab.shape[0]),
+                                             _ptr(guard), _stream())
+    elif guard is not None:
+        rc = _lib.lib().dl_adamw_step_guarded(*lead, float(weight_decay), *tail, guard.data_ptr(), _stream())
+    else:
+        rc = _lib.lib().dl_adamw_step(*lead, float(weight_decay), *tail, _stream())
+    check(rc, "dl_" + who)
+
+
 def adamw_step(param, grad, exp_avg, exp_avg_sq, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, step,
                grad_scale=1.0, lowp=None):
-    n = param.numel()
-    check(_lib.lib().dl_adamw_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
-                                   float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
-                                   float(grad_scale), _ptr(lowp), _DT[lowp.dtype] if lowp is not None else 0,
-                                   _stream()), "dl_adamw_step")
+    _adamw("adamw_step", param, grad, exp_avg, exp_avg_sq, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+           step=step, grad_scale=grad_scale, lowp=lowp)
 
 
 # ---- gradient guard (csrc/grad_guard.hip): global-norm clipping and the non-finite step skip, decided on the device ----
@@ -895,34 +937,22 @@ def grad_guard_finalize(acc, guard, counters, *, pre_scale: float = 1.0, max_nor
 def adamw_step_guarded(param, grad, exp_avg, exp_avg_sq, guard, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, step,
                        grad_scale=1.0, lowp=None):
     """adamw_step with the gradient scaled by grad_scale * guard[0]; writes nothing when guard[2] != 0."""
-    n = param.numel()
-    check(_lib.lib().dl_adamw_step_guarded(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
-                                           float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
-                                           float(grad_scale), _ptr(lowp), _DT[lowp.dtype] if lowp is not None else 0,
-                                           guard.data_ptr(), _stream()), "dl_adamw_step_guarded")
+    if guard is None:
+        raise ValueError("adamw_step_guarded: guard is None")
+    _adamw("adamw_step_guarded", param, grad, exp_avg, exp_avg_sq, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+           weight_decay=weight_decay, step=step, grad_scale=grad_scale, lowp=lowp, guard=guard)
 
 
 def adamw_step_groups(param, grad, exp_avg, exp_avg_sq, quad_group, group_tab, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, step,
                       grad_scale=1.0, lowp=None, guard=None):
-    """adamw_step (guard None) / adamw_step_guarded with a learning-rate scale and a weight decay per group (csrc/adamw_groups.hip):
+    """adamw_step (guard None) / adamw_step_guarded with a learning-rate scale and a weight decay per group (csrc/optim.hip):
     quad_group, uint8, one id per 16-byte chunk of param (ceil(n / 4) entries); group_tab, fp32 (n_groups, 2) rows
     {lr_scale, weight_decay}.  A maximal segment of equal id gets the bits of adamw_step[_guarded] on that segment alone with
     lr = float32(lr) * float32(lr_scale) and that decay; a chunk whose id has no row is not touched."""
-    n = param.numel()
-    _need_gpu(param, grad, exp_avg, exp_avg_sq, quad_group, group_tab, guard)
-    if quad_group.dtype != torch.uint8 or not quad_group.is_contiguous() or quad_group.numel() != (n + 3) // 4:
-        raise ValueError("adamw_step_groups: quad_group must be a contiguous uint8 tensor of ceil(n / 4) = %d entries (got %s, %d)"
-                         % ((n + 3) // 4, quad_group.dtype, quad_group.numel()))
-    if group_tab.dtype != torch.float32 or not group_tab.is_contiguous() or group_tab.dim() != 2 or group_tab.shape[1] != 2:
-        raise ValueError("adamw_step_groups: group_tab must be a contiguous float32 (n_groups, 2) tensor (got %s, %s)"
-                         % (group_tab.dtype, tuple(group_tab.shape)))
-    if guard is not None and (guard.dtype != torch.float32 or guard.numel() < 4):
-        raise ValueError("adamw_step_groups: guard must hold 4 float32 values")
-    check(_lib.lib().dl_adamw_step_groups(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
-                                          float(lr), float(beta1), float(beta2), float(eps), int(step), float(grad_scale),
-                                          _ptr(lowp), _DT[lowp.dtype] if lowp is not None else 0, quad_group.data_ptr(),
-                                          group_tab.data_ptr(), int(group_tab.shape[0]), _ptr(guard), _stream()),
-          "dl_adamw_step_groups")
+    if quad_group is None or group_tab is None:
+        raise ValueError("adamw_step_groups: quad_group and group_tab are required")
+    _adamw("adamw_step_groups", param, grad, exp_avg, exp_avg_sq, lr=lr, beta1=beta1, beta2=beta2, eps=eps, step=step,
+           grad_scale=grad_scale, lowp=lowp, guard=guard, quad_group=quad_group, group_tab=group_tab)
 
 
 class GradGuard:
@@ -949,7 +979,7 @@ class GradGuard:
         return self.guard
 
 
-# ---- weight EMA (csrc/ema.hip): a shadow of the parameter arena moved towards the live parameters -----------------------
+# ---- weight EMA (csrc/optim.hip): a shadow of the parameter arena moved towards the live parameters -----------------------
 def ema_update(ema, param, weight: float, guard=None):
     """ema += weight * (param - ema) in place, fp32, lerp form (ema == param is a bitwise fixed point); param is not written.
     guard (ops.GradGuard.guard or None): nothing is written when guard[2] != 0.  Alignment, the weight's range [0, 1], empty

@@ -3,7 +3,7 @@ parameters, and freezing.
 
 The optimiser keeps its one launch per contiguous run of parameters: the group of every 16-byte chunk of the flat arena is a
 byte of a device table (`quad_group`), the groups' values are rows of a second one (`group_tab`), and dl_adamw_step_groups
-(csrc/adamw_groups.hip) looks both up per chunk.  A host-side split of the runs at every group boundary would turn the one to
+(csrc/optim.hip) looks both up per chunk.  A host-side split of the runs at every group boundary would turn the one to
 three launches of an optimiser into a couple of hundred: biases and norm weights interleave with matrices.
 
     groups = [ParamGroup("no_decay", max_ndim=1, weight_decay=0.0),

@@ -248,19 +248,16 @@ class FusedAdamW:
         device's decision."""
         gr = self.groups
         for s, e, first in self.flat.runs(idx, lambda i: self.steps[i]):
+            run = (self.flat.arena[s:e], self.flat.grads[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e])
+            kw = dict(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step=self.steps[first] + 1,
+                      grad_scale=grad_scale)
+            # one launch per run, through the public name of its form (the three differ in their signatures alone)
             if gr is not None:
-                ops.adamw_step_groups(self.flat.arena[s:e], self.flat.grads[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e],
-                                      gr.quad_group[s // 4:e // 4], gr.group_tab, lr=self.lr, beta1=self.betas[0],
-                                      beta2=self.betas[1], eps=self.eps, step=self.steps[first] + 1, grad_scale=grad_scale,
-                                      guard=guard)
-                continue
-            kw = dict(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
-                      step=self.steps[first] + 1, grad_scale=grad_scale)
-            if guard is None:
-                ops.adamw_step(self.flat.arena[s:e], self.flat.grads[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e], **kw)
+                ops.adamw_step_groups(*run, gr.quad_group[s // 4:e // 4], gr.group_tab, guard=guard, **kw)
+            elif guard is not None:
+                ops.adamw_step_guarded(*run, guard, weight_decay=self.wd, **kw)
             else:
-                ops.adamw_step_guarded(self.flat.arena[s:e], self.flat.grads[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e],
-                                       guard, **kw)
+                ops.adamw_step(*run, weight_decay=self.wd, **kw)
         for i in idx:
             self.steps[i] += 1
 
@@ -432,32 +429,11 @@ class GraphedStep:
                      for b in batch)
 
     def _body(self):
-        tr, m = self.tr, self.tr.model
+        tr = self.tr
         ops.seed_offset_tensor(tr.device).add_(1)
-        feat_d, feat_p, labels, llm_d, llm_p = self.static
         # (hints: by-value knowledge of the capture — the block sizes are part of the graph key, the table CONTENTS are refilled)
-        _, _, ssl_input, cm_input, score = m(feat_d, feat_p, llm_d, llm_p, hints=self.hints)
-        tr._zero_grad()
-        if tr.cls_loss is not None:
-            _, cls_loss = classification_loss(score, labels, tr.cls_loss, self.weights)
-        else:
-            _, cls_loss = binary_cross_entropy(score, labels) if tr.n_class == 1 else cross_entropy_logits(score, labels)
-        out = {"cls": cls_loss.detach()}
-        if "ssl" in self.kind:
-            with m._glue(), Fn.deferred_bn_ticks():     # (the heads' BatchNorm step counters advance in one launch)
-                d = m.ssl_model(**ssl_input)
-            ssl_loss = (d["prot_ssl"] + d["drug_ssl"]) * 0.1
-            if self.kind == "ssl":               # with the CM head behind it this backward is dead too
-                ssl_loss.backward()
-            out["ssl"] = ssl_loss.detach()
-        if "cm" in self.kind:
-            with m._glue():
-                cm_loss = m.cm_model(**cm_input, labels=self.labels)
-            cm_loss = cm_loss * tr.cm_weight
-            cm_loss.backward()
-            out["cm"] = cm_loss.detach()
-        elif self.kind == "cls":
-            cls_loss.backward()
+        out, _ = tr._forward_backward(self.static, "ssl" in self.kind, "cm" in self.kind, hints=self.hints, weights=self.weights,
+                                      cm_labels={"labels": self.labels})
         idx = tr.flat.pack_grads()
         self.reduced = False
         if tr.graph_allreduce and (tr.world > 1 or tr.graph_allreduce == "force"):
@@ -980,12 +956,27 @@ class Trainer:
             if len(self._eager_seen) > 256:            # bounded bookkeeping (signatures of shapes seen once and never again)
                 self._eager_seen.clear()
             self._eager_seen[key] = self._eager_seen.get(key, 0) + 1
-        feat_d, feat_p, labels, llm_d, llm_p = batch
         kind_now = "cm" if compute_cm else "ssl" if compute_ssl else "cls"
-        _, _, ssl_input, cm_input, score = m(feat_d, feat_p, llm_d, llm_p, hints=self.hints_of(meta, batch, kind=kind_now, caps=eager_caps))
+        out, last = self._forward_backward(batch, compute_ssl, compute_cm, hints=self.hints_of(meta, batch, kind=kind_now, caps=eager_caps),
+                                           weights=w_host, ssl_masks=ssl_masks, cm_labels={"meta": meta},
+                                           cm_autoscale=cur_epoch == self.cm_init_epoch)
+        self._finish_step(self._reduce_and_pack(last), compute_ssl, compute_cm, out)
+        return out
+
+    def _forward_backward(self, batch, compute_ssl: bool, compute_cm: bool, *, hints, weights, cm_labels: dict, ssl_masks=None,
+                          cm_autoscale: bool = False):
+        """The body of a step, eager or under capture (GraphedStep._body): forward, classification loss, SSL head, CM head and
+        the backward passes; returns (losses, the backward the optimisers consume).  What the two callers do differently is
+        an argument: the hints, the per-sample weights (host or device, or None), ssl_masks, how the CM head gets its labels
+        (cm_labels: {"meta": ...} or {"labels": ...}) and cm_autoscale, the cm_init_epoch step that scales cm_weight from the two
+        losses — eager only, it reads the host.  The backward of head X runs when X is the last head or run_dead_backward is
+        set; a captured step never has run_dead_backward."""
+        m = self.model
+        feat_d, feat_p, labels, llm_d, llm_p = batch
+        _, _, ssl_input, cm_input, score = m(feat_d, feat_p, llm_d, llm_p, hints=hints)
         self._zero_grad()
         if self.cls_loss is not None:
-            _, cls_loss = classification_loss(score, labels, self.cls_loss, None if w_host is None else w_host.to(self.device))
+            _, cls_loss = classification_loss(score, labels, self.cls_loss, None if weights is None else weights.to(self.device))
         else:
             _, cls_loss = binary_cross_entropy(score, labels) if self.n_class == 1 else cross_entropy_logits(score, labels)
         last = "cm" if compute_cm else "ssl" if compute_ssl else "cls"     # the backward the optimisers consume
@@ -1008,8 +999,8 @@ class Trainer:
         if compute_cm:
             self._zero_grad()
             with m._glue():
-                cm_loss = m.cm_model(**cm_input, meta=meta)
-            if cur_epoch == self.cm_init_epoch:
+                cm_loss = m.cm_model(**cm_input, **cm_labels)
+            if cm_autoscale:
                 c, l = float(cm_loss.detach()), float(cls_loss.detach())
                 if c > 0:
                     while c * self.cm_weight / 10 > l:
@@ -1020,19 +1011,22 @@ class Trainer:
             self._arm(last, "cm")
             cm_loss.backward()
             out["cm"] = cm_loss.detach()
-        idx = self._reduce_and_pack(last)
+        return out, last
+
+    def _finish_step(self, idx: List[int], ssl: bool, cm: bool, out: dict):
+        """The tail of a step, eager or replayed, from the reduced gradients of `idx` on: the guard's decision ("grad_norm" goes
+        into `out`), the optimiser steps, the EMA update, the weight images' epoch and the padding guards' poll copy."""
         scale = 1.0 / self.world
         guard = self._decide_grad_guard(idx, out)
         self.opt.step(idx, scale, guard)
-        if compute_ssl:
+        if ssl:
             self.opt_ssl.step(idx, scale, guard)
-        if compute_cm:
+        if cm:
             self.opt_cm.step(idx, scale, guard)
         if self.ema is not None:
             self.ema.update(guard)
         Fn.bump_param_epoch()
         self._post_guard()
-        return out
 
     # -- gradient guard ---------------------------------------------------------------------------------------------------
     def _decide_grad_guard(self, idx: List[int], out: dict):
@@ -1184,25 +1178,14 @@ class Trainer:
         return g
 
     def _graphed_step(self, g: "GraphedStep", batch, meta=None, weights=None) -> Dict[str, float]:
-        kind = g.kind
         self._graphs[g.key] = self._graphs.pop(g.key)                        # most recently used last
         out, idx = g.run(batch, meta, weights)
         if self.world > 1 and not g.reduced:
             idx = self._agreed(g.last, idx)
             self._all_reduce_runs(idx)
-        guard = None
         if self.grad_guard is not None:
             out = dict(out)                  # (the graph's own result dict stays as captured)
-            guard = self._decide_grad_guard(idx, out)
-        self.opt.step(idx, 1.0 / self.world, guard)
-        if "ssl" in kind:
-            self.opt_ssl.step(idx, 1.0 / self.world, guard)
-        if "cm" in kind:
-            self.opt_cm.step(idx, 1.0 / self.world, guard)
-        if self.ema is not None:
-            self.ema.update(guard)
-        Fn.bump_param_epoch()
-        self._post_guard()
+        self._finish_step(idx, "ssl" in g.kind, "cm" in g.kind, out)
         self._replays_since_sync += 1
         if self.graph_sync_every and self._replays_since_sync >= self.graph_sync_every:
             torch.cuda.current_stream(self.device).synchronize()

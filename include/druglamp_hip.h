@@ -892,6 +892,8 @@ int dl_triplet_sigcos_bwd(const float* p_lats, const float* d_lats, const int8_t
  * Fused AdamW over a flat fp32 parameter arena (torch.optim.AdamW semantics, decoupled weight
  * decay, bias correction; trainer.py:225-229 steps up to three of these per batch).
  * step is the 1-based step count AFTER increment.  Optionally emits a compute-dtype copy.
+ * DL_ERR_ARG before anything is launched: a null pointer, n <= 0, step < 1, n beyond one grid (2^31 - 1 workgroups of 1024
+ * elements); the same holds for dl_adamw_step_guarded and dl_adamw_step_groups below.
  * ------------------------------------------------------------------------------------------ */
 int dl_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                   float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
@@ -938,8 +940,9 @@ int dl_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float
  *
  * dl_adamw_step_groups: quad_group holds ceil(n / 4) bytes, quad_group[q] = the group id k of elements 4q .. 4q+3 (the flat
  *   arena pads every parameter to a multiple of 4 elements: a chunk belongs to one parameter); group_tab holds n_groups rows
- *   of 2 floats {lr_scale, weight_decay}.  The chunk is updated by dl_adamw_step's arithmetic (csrc/adamw.cuh, the single
- *   definition) with lr_k = lr * group_tab[2k], ONE fp32 multiply, and weight_decay = group_tab[2k + 1].
+ *   of 2 floats {lr_scale, weight_decay}.  The chunk is updated by dl_adamw_step's arithmetic (csrc/optim.hip: the three
+ *   dl_adamw_step* entry points launch one kernel, adamw_kernel, from one host launcher) with lr_k = lr * group_tab[2k],
+ *   ONE fp32 multiply, and weight_decay = group_tab[2k + 1].
  *   Bit contract: for every maximal segment of equal group id, param, exp_avg, exp_avg_sq and param_lowp hold the bits of
  *   dl_adamw_step (guard null) / dl_adamw_step_guarded (guard given) called on that segment alone with lr = (float)lr *
  *   (float)lr_scale and that weight decay.

@@ -1,4 +1,4 @@
-"""fp64 restatement of the weight EMA (csrc/ema.hip; contract in include/druglamp_hip.h; trainer.WeightEMA): the recurrence
+"""fp64 restatement of the weight EMA (csrc/optim.hip; contract in include/druglamp_hip.h; trainer.WeightEMA): the recurrence
 e + w (p - e) with the weight the C ABI receives (w rounded to fp32), the weight schedule, the element-wise bound of the GPU
 tests and an fp32 emulation of the kernel's arithmetic.  numpy / torch on the CPU.
 """

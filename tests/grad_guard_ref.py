@@ -1,4 +1,4 @@
-"""fp64 restatement of the gradient guard (csrc/grad_guard.hip; contract in include/druglamp_hip.h): the sum of squares, the
+"""fp64 restatement of the gradient guard (csrc/grad_guard.hip, the guarded AdamW step of csrc/optim.hip; contract in include/druglamp_hip.h): the sum of squares, the
 finalize decision and the guarded AdamW step.  numpy / torch on the CPU; the scalars are the fp32 values the C ABI receives.
 """
 import math

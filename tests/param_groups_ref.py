@@ -1,4 +1,4 @@
-"""fp64 restatement of dl_adamw_step_groups (csrc/adamw_groups.hip) for the tests: tests/elem_ref.adamw with a learning rate and
+"""fp64 restatement of dl_adamw_step_groups (csrc/optim.hip) for the tests: tests/elem_ref.adamw with a learning rate and
 a weight decay per 16-byte chunk.  As there, the scalars are first rounded to the fp32 values the C ABI receives; the group's
 learning rate is the fp32 PRODUCT float32(lr) * float32(lr_scale) (the kernel's one fp32 multiply), the guarded gradient scale
 the fp32 product float32(gscale) * float32(guard[0]); everything else is fp64."""

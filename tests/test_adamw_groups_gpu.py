@@ -1,4 +1,4 @@
-"""dl_adamw_step_groups (csrc/adamw_groups.hip) through druglamp_amd.ops: the bit contract of include/druglamp_hip.h.
+"""dl_adamw_step_groups (csrc/optim.hip) through druglamp_amd.ops: the bit contract of include/druglamp_hip.h.
 
 For every maximal segment of equal group id the result is dl_adamw_step (guard null) / dl_adamw_step_guarded on that segment
 alone with lr = float32(lr) * float32(lr_scale) and the group's weight decay, BIT FOR BIT, in param, exp_avg, exp_avg_sq and

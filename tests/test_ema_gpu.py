@@ -1,4 +1,4 @@
-"""The weight-EMA kernel (csrc/ema.hip) through druglamp_amd.ops, against tests/ema_ref.py.
+"""The weight-EMA kernel (csrc/optim.hip) through druglamp_amd.ops, against tests/ema_ref.py.
 
   * parity: every element within 2^-22 max(|e|, |p|) of the fp64 recurrence (derived in ema_ref.bound, checked on an fp32
     emulation in tests/test_ema_reference_cpu.py), param never written, at sizes that take every path of the launch shape:

@@ -1,4 +1,4 @@
-"""The gradient-guard kernels (csrc/grad_guard.hip) through druglamp_amd.ops, against tests/grad_guard_ref.py.
+"""The gradient-guard kernels (csrc/grad_guard.hip; dl_adamw_step_guarded: csrc/optim.hip) through druglamp_amd.ops, against tests/grad_guard_ref.py.
 
   * dl_grad_sqnorm: the fp64 sum of the exactly squared fp32 data to a relative n 2^-53 (the bound of ANY summation order in
     fp64 for positive terms — derived, not measured), bitwise repeatable, at sizes that take every path of the launch shape:
