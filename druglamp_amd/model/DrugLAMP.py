@@ -19,7 +19,8 @@ class DrugLAMP(DrugLAMPBase):
             return self._forward(vd, vp, xd, xp, mode, hints)
 
     def _forward(self, vd, vp, xd, xp, mode, hints=None):
-        if self.branch_streams and hints is not None and hints.branch_streams and xp.is_cuda:
+        # (never with dynamic tile hand-out: the ticket words are per device and hold for launches ordered on ONE stream)
+        if self.branch_streams and hints is not None and hints.branch_streams and xp.is_cuda and not ops.dynamic_tiles_enabled():
             return self._forward_branches(vd, vp, xd, xp, mode, hints)
         vd = self.drug_extractor(vd)
         # one pass over each LLM tensor: fill bit + (site-pooled) fill-bit-augmented features, already padded

@@ -272,6 +272,10 @@ def flush_reductions() -> None:
 # Dynamic tile hand-out of the persistent large-tile GEMM (dl_gemm_args.tile_tickets): on while gradient buckets are being
 # all-reduced DURING backward (trainer.GradOverlap), when RCCL channel workgroups occupy some CUs for a while — a CU that
 # starts late then simply takes fewer tiles.  Two int32 per device, zero between launches (the kernel restores them).
+# ONE pair of words per device, not per stream: the last workgroup of a launch zeroes them for the next launch ON ITS
+# STREAM, so they are valid only for ticketed launches that are ordered on one stream — two such launches running at once
+# on different streams would draw from one counter and each would skip tiles.  The switch is process-global; the models
+# therefore keep their forward on one stream while it is on (dynamic_tiles_enabled(): DrugLAMP._forward).
 _tickets = {}
 _tickets_on = False
 
@@ -279,6 +283,11 @@ _tickets_on = False
 def dynamic_tiles(on: bool) -> None:
     global _tickets_on
     _tickets_on = bool(on)
+
+
+def dynamic_tiles_enabled() -> bool:
+    """True while the large-tile GEMMs draw their tiles from the per-device ticket words (one stream only, see above)."""
+    return _tickets_on
 
 
 def reset_tickets() -> None:
