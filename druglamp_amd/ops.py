@@ -838,6 +838,20 @@ def next_seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,), generator=_seed_gen).item())
 
 
+def seed_state(device) -> dict:
+    """What the dropout sites of the next step depend on, for a checkpoint: the site-seed generator's state (a CPU byte
+    tensor), the device-resident offset's value (reading it waits for the device) and whether the offset is in use."""
+    return {"generator": _seed_gen.get_state().clone(), "offset": int(seed_offset_tensor(device).item()), "offset_on": bool(_seed_offset_on)}
+
+
+def set_seed_state(state: dict, device) -> None:
+    """Put a seed_state() back.  Generator, offset and the switch are process-global: every model of the process draws from
+    them."""
+    _seed_gen.set_state(state["generator"].to(torch.uint8).cpu())
+    seed_offset_tensor(device).fill_(int(state["offset"]))
+    use_seed_offset(bool(state["offset_on"]))
+
+
 def rowmod_sum(x2d: torch.Tensor, L: int) -> torch.Tensor:
     M, D = x2d.shape
     out = torch.empty((L, D), dtype=torch.float32, device=x2d.device)
@@ -986,6 +1000,15 @@ class GradGuard:
         grad_guard_finalize(self.acc, self.guard, self.counters, pre_scale=pre_scale, max_norm=self.max_norm,
                             skip_nonfinite=self.skip_nonfinite)
         return self.guard
+
+    def state(self) -> dict:
+        """For a checkpoint: the cumulative counters {skipped, clipped} and the last decision (what grad_guard_stats reads);
+        the sum and the workspace are rewritten by every decision."""
+        return {"counters": self.counters.detach().cpu(), "guard": self.guard.detach().cpu()}
+
+    def load_state(self, state: dict) -> None:
+        self.counters.copy_(state["counters"])
+        self.guard.copy_(state["guard"])
 
 
 # ---- weight EMA (csrc/optim.hip): a shadow of the parameter arena moved towards the live parameters -----------------------

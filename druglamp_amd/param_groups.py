@@ -126,6 +126,29 @@ class ParamGroups:
         """[(group name, parameter name, numel)] in parameter order, for logging."""
         return [(self.names[k], n, p.numel()) for n, p, k in self._params]
 
+    def assignment(self) -> List[list]:
+        """[[parameter name, group name, frozen]] in parameter order: what a checkpoint's signature records."""
+        return [[n, self.names[k], bool(self.frozen[k])] for n, _, k in self._params]
+
+    def state(self) -> dict:
+        """The groups' current values, set_param_group's changes included: {"names": [...], "rows": [[lr_scale, weight_decay]]}."""
+        return {"names": list(self.names), "rows": [[float(s), float(w)] for s, w in self.rows]}
+
+    def check_state(self, state: dict) -> None:
+        """ValueError unless `state` is a state() of these groups with valid values (nothing is written)."""
+        if list(state.get("names", ())) != self.names or len(state.get("rows", ())) != len(self.names):
+            raise ValueError("ParamGroups: the saved groups %s are not this trainer's %s" % (list(state.get("names", ())), self.names))
+        for n, row in zip(self.names, state["rows"]):
+            _value("ParamGroups: saved group %r: lr_scale" % n, row[0])
+            _value("ParamGroups: saved group %r: weight_decay" % n, row[1])
+
+    def load_state(self, state: dict) -> None:
+        """Take every group's values from a state() and rewrite the device table (one small copy, between steps)."""
+        self.check_state(state)
+        self.rows = [(float(s), float(w)) for s, w in state["rows"]]
+        if self.group_tab is not None:
+            self.group_tab.copy_(torch.tensor(self.rows, dtype=torch.float32).reshape(len(self.rows), 2))
+
     def values(self, name: str) -> Tuple[float, float]:
         """(lr_scale, weight_decay) of a group as the host knows them."""
         if name not in self.names:

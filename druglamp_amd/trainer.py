@@ -28,7 +28,11 @@ What is new (MI355X-native):
     (meta "Weight") and the focal term as one dl_cls_loss_fwd / dl_cls_loss_bwd launch pair in place of the torch loss tail;
   * optional parameter groups (Trainer(param_groups=[ParamGroup(...)]), param_groups.py): a learning-rate scale and a weight decay
     per group and frozen parts, with the group looked up per 16-byte chunk inside the optimiser kernel (dl_adamw_step_groups) —
-    the launches per optimiser stay the one to three of its runs.
+    the launches per optimiser stay the one to three of its runs;
+  * checkpoints (Trainer.save_checkpoint / load_checkpoint, fit(checkpoint_dir=..., resume=True); the file: checkpoint.py):
+    everything a step reads or writes outside the model — moments, step counts, schedules, EMA, guard counters, group values,
+    the random generators of every rank — in one file beside the state_dict, so that a run resumes bit for bit; no kernel,
+    and nothing changes for a trainer that never saves or loads.
 """
 from __future__ import annotations
 
@@ -37,13 +41,16 @@ import contextlib
 import dataclasses
 import math
 import os
+import warnings
 from typing import Dict, List, Optional, Sequence
 
 import torch
 import torch.distributed as dist
 
+from . import checkpoint as ckpt
 from . import functional as Fn
 from . import ops
+from .checkpoint import check_tensor
 from .cls_loss import ClsLoss, classification_loss, meta_weights
 from .param_groups import ParamGroup, ParamGroups
 from .model.basic_model import binary_cross_entropy, cross_entropy_logits
@@ -77,6 +84,13 @@ class CosineAnnealingWarmupRestarts:
             self.lr = self.min_lr + (self.max_lr - self.min_lr) * (
                 1 + math.cos(math.pi * (s - self.warmup_steps) / (self.first_cycle_steps - self.warmup_steps))) / 2
         return self.lr
+
+    def state(self) -> dict:
+        """Where the schedule stands, for a checkpoint."""
+        return {"step_in_cycle": int(self.step_in_cycle), "cycle": int(self.cycle), "lr": float(self.lr)}
+
+    def load_state(self, state: dict) -> None:
+        self.step_in_cycle, self.cycle, self.lr = int(state["step_in_cycle"]), int(state["cycle"]), float(state["lr"])
 
 
 class FlatParams:
@@ -261,6 +275,26 @@ class FusedAdamW:
         for i in idx:
             self.steps[i] += 1
 
+    def state(self) -> dict:
+        """Both moments (copied to the CPU), the per-parameter step counts and the learning rate, for a checkpoint."""
+        return {"exp_avg": self.exp_avg.detach().cpu(), "exp_avg_sq": self.exp_avg_sq.detach().cpu(), "steps": list(self.steps),
+                "lr": float(self.lr)}
+
+    def check_state(self, state: dict, what: str = "optimiser") -> None:
+        """RuntimeError unless `state` is a state() of an optimiser over this arena (nothing is written)."""
+        for k in ("exp_avg", "exp_avg_sq"):
+            check_tensor("%s.%s" % (what, k), state.get(k), self.exp_avg.shape, torch.float32)
+        steps = state.get("steps")
+        if not isinstance(steps, list) or len(steps) != len(self.steps) or any(not isinstance(s, int) or s < 0 for s in steps):
+            raise RuntimeError("checkpoint: %s.steps must be %d step counts" % (what, len(self.steps)))
+        float(state["lr"])
+
+    def load_state(self, state: dict) -> None:
+        self.exp_avg.copy_(state["exp_avg"])
+        self.exp_avg_sq.copy_(state["exp_avg_sq"])
+        self.steps = [int(s) for s in state["steps"]]
+        self.lr = float(state["lr"])
+
 
 class WeightEMA:
     """An exponential moving average of the parameters on a FlatParams: `shadow`, an fp32 clone of the arena taken at
@@ -286,6 +320,14 @@ class WeightEMA:
         """guard (ops.GradGuard.guard): nothing is written when guard[2] != 0; `updates` advances either way."""
         ops.ema_update(self.shadow, self.flat.arena, self.weight(), guard)
         self.updates += 1
+
+    def state(self) -> dict:
+        """The shadow (copied to the CPU) and the update count, for a checkpoint."""
+        return {"shadow": self.shadow.detach().cpu(), "updates": int(self.updates)}
+
+    def load_state(self, state: dict) -> None:
+        self.shadow.copy_(state["shadow"])
+        self.updates = int(state["updates"])
 
 
 class GraphedStep:
@@ -587,6 +629,7 @@ class Trainer:
         self.skip_nonfinite = bool(skip_nonfinite)
         self.model = model
         self.cfg = cfg
+        self.compute_dtype, self.freeze_bn = compute_dtype, bool(freeze_bn)     # (recorded in a checkpoint's signature)
         if freeze_bn:
             if bool(cfg["RS"]["SSL"]) or bool(cfg["RS"]["CM"]):
                 raise ValueError("Trainer(freeze_bn=True) runs cls steps only: the SSL and CM step kinds are not supported with "
@@ -1210,6 +1253,205 @@ class Trainer:
             self.model.cm_model.step()
         self.check_device_flags()                      # (an epoch boundary: a host sync costs nothing here)
 
+    # -- checkpoints (checkpoint.py: the file format and its checks) --------------------------------------------------------
+    def _opt_schd(self):
+        """[(name, optimiser, its scheduler)] of the optimisers that exist."""
+        return [(n, o, s) for n, o, s in (("opt", self.opt, self.schd), ("opt_ssl", self.opt_ssl, self.schd_ssl),
+                                          ("opt_cm", self.opt_cm, self.schd_cm)) if o is not None]
+
+    def checkpoint_signature(self) -> dict:
+        """What a checkpoint of this trainer is valid for (checkpoint.MUST_MATCH: a load is refused on a difference;
+        checkpoint.WARN_ONLY: a load warns)."""
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        return {
+            "model": type(self.model).__name__,
+            "params": [[names[id(p)], list(p.shape), off] for p, off in zip(self.flat.params, self.flat.offsets)],
+            "compute_dtype": str(self.compute_dtype).split(".")[-1],
+            "world": int(self.world),
+            "optimisers": [n for n, _, _ in self._opt_schd()],
+            "ema": {"on": self.ema is not None, "decay": None if self.ema is None else self.ema.decay,
+                    "warmup": None if self.ema is None else self.ema.warmup},
+            "guard": {"on": self.grad_guard is not None, "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite},
+            "freeze_bn": self.freeze_bn,
+            "cls_loss": None if self.cls_loss is None else dataclasses.asdict(self.cls_loss),
+            "param_groups": None if self.param_groups is None else self.param_groups.assignment(),
+            "graph_steps": self.graph_steps,
+            "fixed_caps": None if self.fixed_caps is None else list(self.fixed_caps),
+        }
+
+    def _gather_host(self, t: torch.Tensor) -> List[torch.Tensor]:
+        """A small CPU tensor of every rank, in rank order (a list of one at world size 1; a collective otherwise)."""
+        if self.world <= 1:
+            return [t]
+        mine = t.to(self.device) if dist.get_backend() == "nccl" else t
+        out = [torch.empty_like(mine) for _ in range(self.world)]
+        dist.all_gather(out, mine)
+        return [o.cpu() for o in out]
+
+    def _rng_state(self) -> dict:
+        """The random state a step consumes, per rank: the dropout site-seed generator, the device-resident seed offset (and
+        whether it is in use), torch's CPU generator and torch's device generator (the MLM mask draw of the SSL heads)."""
+        seed = ops.seed_state(torch.device(self.device))
+        on_gpu = torch.device(self.device).type == "cuda"
+        dev_state = torch.cuda.get_rng_state(self.device) if on_gpu else torch.zeros(0, dtype=torch.uint8)
+        return {"seed_gen": self._gather_host(seed["generator"]),
+                "seed_offset": [int(t) for t in self._gather_host(torch.tensor([seed["offset"]], dtype=torch.int64))],
+                "seed_offset_on": seed["offset_on"],
+                "cpu": self._gather_host(torch.get_rng_state()),
+                "device": self._gather_host(dev_state)}
+
+    def save_checkpoint(self, path, extra: Optional[dict] = None) -> None:
+        """Write everything a later load_checkpoint needs to go on from here bit for bit, as one file (checkpoint.py: the
+        layout; the file is also a weight file that load_reference_checkpoint accepts).  Call it between steps: it
+        synchronises the device once and runs check_device_flags() first — the checkpoint of a step that tripped a guard is
+        refused (RuntimeError, nothing written).  Saved: the model's state_dict (parameters, buffers, the lazily created
+        SimSiam projectors once they exist); per optimiser both moments, the step counts and the lr; the schedulers;
+        cm_weight and the cross-modality head's margin schedule; the EMA shadow and its update count; the guard counters;
+        the parameter groups' current values; fixed_caps; the random state of every rank (_rng_state); `extra`, a dict of
+        plain data (tensors, scalars, strings, lists, dicts) that load_checkpoint returns.  Not saved, because they are
+        rebuilt: the gradient buffer, captured graphs and their bookkeeping, agreed gradient sets, weight images, workspaces.
+        The write is atomic (an existing file survives a failed write).  At world > 1 EVERY rank calls this (the ranks' random
+        states are gathered), rank 0 writes, and all ranks leave together once the file exists.
+        A trainer that saved launches exactly what it launches otherwise: no hook, stream or flag is left behind."""
+        if self._ema_swapped:
+            raise RuntimeError("Trainer.save_checkpoint inside ema_weights(): the arena holds the averaged weights")
+        if torch.device(self.device).type == "cuda":
+            torch.cuda.synchronize(self.device)
+        self.check_device_flags()
+        cm = getattr(self.model, "cm_model", None)
+        state = {
+            "optimisers": {n: o.state() for n, o, _ in self._opt_schd()},
+            "schedulers": {n: s.state() for n, _, s in self._opt_schd()},
+            "cm_weight": float(self.cm_weight),
+            # (the margin schedule of the CM head is host state outside its state_dict: on_train_epoch_end steps it)
+            "cm_margin": None if cm is None else {"step": int(cm.m_sch_loss_fn._step), "m_cur": float(cm.m_sch_loss_fn.m_cur)},
+            "ema": None if self.ema is None else self.ema.state(),
+            "grad_guard": None if self.grad_guard is None else self.grad_guard.state(),
+            "param_groups": None if self.param_groups is None else self.param_groups.state(),
+            "fixed_caps": None if self.fixed_caps is None else list(self.fixed_caps),
+            "rng": self._rng_state(),
+        }
+        err = None
+        if self.rank == 0:
+            try:
+                ckpt.write(ckpt.pack(self.model.state_dict(), state, self.checkpoint_signature(), extra), path)
+            except BaseException as e:          # (the other ranks wait at the barrier below: reach it before raising)
+                if self.world <= 1:
+                    raise
+                err = e
+        if self.world > 1:
+            dist.barrier()
+            if err is not None:
+                raise err
+
+    def _check_checkpoint(self, blob: dict, path) -> List[str]:
+        """Everything load_checkpoint checks before it writes; returns the warning lines.  RuntimeError names the difference."""
+        notes = ckpt.validate(blob, self.checkpoint_signature(), "Trainer.load_checkpoint(%s)" % (path,))
+        sd, own = blob["state_dict"], self.model.state_dict()
+        lazy = lambda k: ".projector." in k             # noqa: E731  (the SimSiam projectors: in the file once they exist)
+        for k, v in own.items():
+            if k not in sd:
+                if lazy(k):
+                    continue
+                raise RuntimeError("checkpoint: %s has no entry %r in its state_dict" % (path, k))
+            check_tensor("state_dict[%r]" % k, sd[k], v.shape, v.dtype)
+        unknown = [k for k in sd if k not in own and not lazy(k)]
+        if unknown:
+            raise RuntimeError("checkpoint: %s holds %d state_dict entries the model does not have (first: %s)" % (path, len(unknown), unknown[0]))
+        if any(lazy(k) for k in sd) and not hasattr(self.model, "ssl_model"):
+            raise RuntimeError("checkpoint: %s holds SimSiam projectors, the model has no SSL head" % (path,))
+        st = blob["trainer"]
+        n = self.flat.numel
+        for name, o, _ in self._opt_schd():
+            if name not in st.get("optimisers", {}) or name not in st.get("schedulers", {}):
+                raise RuntimeError("checkpoint: %s has no state of %s" % (path, name))
+            o.check_state(st["optimisers"][name], name)
+            sc = st["schedulers"][name]
+            if any(not isinstance(sc.get(k), t) for k, t in (("step_in_cycle", int), ("cycle", int), ("lr", float))):
+                raise RuntimeError("checkpoint: the scheduler state of %s is incomplete" % name)
+        if self.ema is not None:
+            check_tensor("ema.shadow", (st.get("ema") or {}).get("shadow"), (n,), torch.float32)
+            int(st["ema"]["updates"])
+        if self.grad_guard is not None:
+            check_tensor("grad_guard.counters", (st.get("grad_guard") or {}).get("counters"), (2,), torch.int64)
+            check_tensor("grad_guard.guard", st["grad_guard"].get("guard"), (4,), torch.float32)
+        if self.param_groups is not None:
+            try:
+                self.param_groups.check_state(st.get("param_groups") or {})
+            except ValueError as e:
+                raise RuntimeError("checkpoint: %s" % e) from e
+        if getattr(self.model, "cm_model", None) is not None and not isinstance(st.get("cm_margin"), dict):
+            raise RuntimeError("checkpoint: %s has no margin schedule for the cross-modality head" % (path,))
+        float(st["cm_weight"])
+        rng = st.get("rng") or {}
+        for k in ("seed_gen", "cpu", "device", "seed_offset"):
+            if not isinstance(rng.get(k), list) or len(rng[k]) != self.world:
+                raise RuntimeError("checkpoint: %s holds no %s random state for each of the %d ranks" % (path, k, self.world))
+        return notes
+
+    def load_checkpoint(self, path) -> dict:
+        """Take over the state a save_checkpoint wrote; returns the `extra` dict of the save ({} where none was given).
+        EVERYTHING is checked first — the file reads (weights_only=True), its format is known, its signature fits this trainer
+        (model class, parameter names / shapes / arena offsets, world size, which optimisers exist, EMA and guard on or off,
+        the parameter-group assignment: RuntimeError naming the first difference), every tensor has its shape — and only then
+        written: a refused file leaves every tensor and count of the trainer untouched.  A different graph_steps or fixed_caps
+        (and compute dtype, EMA / guard / loss settings, freeze_bn) only warns: the state is the same either way, the trainer
+        keeps its own.  Frozen parameters keep requires_grad=False and still take the file's values.
+        After writing: the parameter epoch is bumped (weight images are refreshed; entity codes and libraries built before the
+        load are refused by their epoch checks), every captured graph and the bookkeeping that keys graphs is dropped (they
+        bake site seeds and capacities of another history; the next steps warm up and capture anew), the device-side
+        parameter-group table is rewritten.  At world > 1 every rank loads the same file (each finds its own random state in
+        it) and replicas_in_sync() is verified.
+        PROCESS-GLOBAL: the dropout site-seed generator, the device seed offset (value and switch) and torch's CPU and
+        device generators belong to the process, not to this trainer.  A load sets them for everything in the process."""
+        if self._ema_swapped:
+            raise RuntimeError("Trainer.load_checkpoint inside ema_weights(): the exit would overwrite the loaded weights")
+        blob = ckpt.read(path)
+        notes = self._check_checkpoint(blob, path)
+        from .model.model_interface import load_reference_checkpoint
+        on_gpu = torch.device(self.device).type == "cuda"
+        if on_gpu:
+            torch.cuda.synchronize(self.device)          # (graphs are released below: nothing of them may still run)
+        st, sd = blob["trainer"], blob["state_dict"]
+        ssl = getattr(self.model, "ssl_model", None)
+        if ssl is not None and not any(".projector." in k for k in sd):
+            ssl.net.projector = ssl.llm_net.projector = None       # (not created yet in the saved history: the first SSL forward draws them)
+        with torch.no_grad():
+            load_reference_checkpoint(self.model, {"state_dict": sd}, strict=True)    # (builds the projectors the file holds first)
+            for name, o, s in self._opt_schd():
+                o.load_state(st["optimisers"][name])
+                s.load_state(st["schedulers"][name])
+            self.cm_weight = float(st["cm_weight"])
+            cm = getattr(self.model, "cm_model", None)
+            if cm is not None:
+                cm.m_sch_loss_fn._step, cm.m_sch_loss_fn.m_cur = int(st["cm_margin"]["step"]), float(st["cm_margin"]["m_cur"])
+            if self.ema is not None:
+                self.ema.load_state(st["ema"])
+            if self.grad_guard is not None:
+                self.grad_guard.load_state(st["grad_guard"])
+            if self.param_groups is not None:
+                self.param_groups.load_state(st["param_groups"])
+        rng, r = st["rng"], self.rank
+        # (a graph-replaying trainer needs the offset whatever the saving one did: one seed regime for its eager and replayed steps)
+        ops.set_seed_state({"generator": rng["seed_gen"][r], "offset": rng["seed_offset"][r],
+                            "offset_on": bool(rng["seed_offset_on"]) or bool(self.graph_steps)}, torch.device(self.device))
+        torch.set_rng_state(rng["cpu"][r])
+        if on_gpu and rng["device"][r].numel():
+            torch.cuda.set_rng_state(rng["device"][r], self.device)
+        Fn.bump_param_epoch()
+        self._graphs.clear()
+        self._eager_seen.clear()
+        self._graph_caps.clear()
+        self._agreed_sets.clear()
+        if self.overlap is not None:
+            self.overlap.expected.clear()
+        self._guard_runs, self._guard_event, self._replays_since_sync = None, None, 0
+        if self.world > 1 and not self.replicas_in_sync():
+            raise RuntimeError("Trainer.load_checkpoint(%s): the replicas are not in sync after the load (did every rank read the same file?)" % (path,))
+        for line in notes:
+            warnings.warn("Trainer.load_checkpoint(%s): %s" % (path, line))
+        return blob["extra"]
+
     # -- evaluation (trainer.py:256-292; torchmetrics replaced by sklearn on the gathered predictions) -----
     @torch.no_grad()
     def predict(self, batches):
@@ -1436,7 +1678,8 @@ class Trainer:
     def _epoch_losses(self, sums, steps) -> Dict[str, float]:
         return _epoch_loss_means(sums, steps, self.world, self.device)
 
-    def fit(self, train_batches, val_batches, epochs: Optional[int] = None, on_epoch=None) -> Dict[str, object]:
+    def fit(self, train_batches, val_batches, epochs: Optional[int] = None, on_epoch=None, checkpoint_dir=None,
+            checkpoint_every: int = 1, resume: bool = False) -> Dict[str, object]:
         """The reference's run_experiment loop (trainer.py:131-135,150-163): one pass over `train_batches()` per epoch
         (a callable yielding (batch, meta) pairs), on_train_epoch_end, validation; the parameters with the best
         `val_ausum` (AUROC + AUPRC: ModelCheckpoint(monitor='val_ausum', mode='max')) are kept, training stops after
@@ -1444,12 +1687,38 @@ class Trainer:
         reloaded before returning (trainer.py:134) — ready for evaluate(test_batches).
         With the weight EMA on, validation runs under ema_weights() (selection and early stopping judge the averaged weights),
         every history entry says so ("weights": "ema"), and the best snapshot holds the live arena, the shadow and the
-        buffers: all three are reloaded."""
+        buffers: all three are reloaded.
+        checkpoint_dir (None: nothing is written and the loop is exactly the one above): a directory, created if need be.
+        After the validation and bookkeeping of every checkpoint_every-th epoch (and of the epoch early stopping ends on)
+        `last.pt` is written there: a save_checkpoint whose `extra` carries the epoch number, `history`, the early-stopping
+        count and the best snapshot (arena, buffers, shadow, epoch, ausum).  Whenever the best snapshot improves, `best.pt` is
+        written: the parameters of that moment as a plain checkpoint (also a weight file for load_reference_checkpoint).
+        resume=True with an existing `last.pt`: load it and go on with the next epoch, same patience arithmetic; the returned
+        history is the whole run's.  Without a `last.pt` the run starts from scratch.  An eager run resumed this way leaves
+        the bits of the uninterrupted run (INTEGRATION.md "Checkpoints and resuming")."""
         epochs = int(epochs or self.epochs)
         patience = max(int(epochs / 4), 1)
         best = {"ausum": -float("inf"), "epoch": 0, "arena": None, "buffers": None, "shadow": None}
-        history, bad = [], 0
-        for ep in range(1, epochs + 1):
+        history, bad, first = [], 0, 1
+        if checkpoint_dir is None and resume:
+            raise ValueError("Trainer.fit(resume=True) needs a checkpoint_dir")
+        if checkpoint_dir is not None:
+            if int(checkpoint_every) < 1:
+                raise ValueError("Trainer.fit: checkpoint_every must be a positive number of epochs")
+            os.makedirs(checkpoint_dir, exist_ok=True)
+            last_path, best_path = os.path.join(checkpoint_dir, "last.pt"), os.path.join(checkpoint_dir, "best.pt")
+            if resume and os.path.exists(last_path):
+                ex = self.load_checkpoint(last_path).get("fit")
+                if ex is None:
+                    raise RuntimeError("Trainer.fit(resume=True): %s was not written by fit" % last_path)
+                history, bad, first = [dict(h) for h in ex["history"]], int(ex["bad"]), int(ex["epoch"]) + 1
+                to_dev = lambda t: None if t is None else t.to(self.device)      # noqa: E731
+                best = {"ausum": float(ex["best"]["ausum"]), "epoch": int(ex["best"]["epoch"]), "arena": to_dev(ex["best"]["arena"]),
+                        "buffers": None if ex["best"]["buffers"] is None else [to_dev(b) for b in ex["best"]["buffers"]],
+                        "shadow": to_dev(ex["best"]["shadow"])}
+                if bad >= patience:                      # (the saved run had stopped early already)
+                    first = epochs + 1
+        for ep in range(first, epochs + 1):
             sums: Dict[str, torch.Tensor] = {}
             steps = 0
             guard_before = self.grad_guard.counters.clone() if self.grad_guard is not None else None
@@ -1480,10 +1749,14 @@ class Trainer:
                             buffers=[b.detach().clone() for b in self.model.buffers()],
                             shadow=self.ema.shadow.clone() if self.ema is not None else None)
                 bad = 0
+                if checkpoint_dir is not None:
+                    self.save_checkpoint(best_path, extra={"epoch": ep, "ausum": float(score)})
             else:
                 bad += 1
-                if bad >= patience:
-                    break
+            if checkpoint_dir is not None and (ep % int(checkpoint_every) == 0 or bad >= patience):
+                self.save_checkpoint(last_path, extra={"fit": {"epoch": ep, "history": history, "bad": bad, "best": best}})
+            if bad >= patience:
+                break
         if best["arena"] is not None:                                    # reload the best checkpoint (trainer.py:134)
             with torch.no_grad():
                 self.flat.arena.copy_(best["arena"])
