@@ -1376,9 +1376,10 @@ class BatchNormWeightedTailFn(torch.autograd.Function):
     mean terms w times.  Returns (y, mean, var)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, rmean, rvar, eps, momentum, LP, lead, w, relu=False):
+    def forward(ctx, x, gamma, beta, rmean, rvar, eps, momentum, LP, lead, w, relu=False, wide_backward=False):
         """relu=True: max(0, .) behind the BatchNorm in the same kernels (as BatchNormRowsFn; the mask is a row's own, so the
-        multiplicities only enter through the sums, exactly as without it)."""
+        multiplicities only enter through the sums, exactly as without it).
+        wide_backward=True: low-precision inputs take the two passes of the backward in fp32 and round once (see backward)."""
         R, C = x.shape
         x = x.contiguous()
         tail = LP - lead
@@ -1386,19 +1387,30 @@ class BatchNormWeightedTailFn(torch.autograd.Function):
         sums = ops.bn_stats(x, LP, 0, lead)
         sums = sums.add_(ops.bn_stats(x, LP, lead, tail), alpha=float(w))
         mean, var, rstd = ops.bn_finalize(sums, n, eps, *_bn_running(momentum, rmean, rvar))
-        ctx.cfg = (LP, lead, w, n, relu)
+        ctx.cfg = (LP, lead, w, n, relu, bool(wide_backward))
         return _bn_apply_and_save(ctx, x, mean, var, rstd, gamma, beta, relu)
 
     @staticmethod
     def backward(ctx, dy, _m, _v):
         x, mean, rstd, g, b = ctx.saved_tensors
-        LP, lead, w, n, relu = ctx.cfg
+        LP, lead, w, n, relu, wide = ctx.cfg
         R, C = x.shape
         # (tail rows of dy already hold the sums over their copies; a row and its copies share the ReLU mask)
-        dx, sums = _bn_train_bwd(dy.contiguous(), x, mean, rstd, g, b, 1.0 / n, relu)
+        # A tail row's dx is g rstd (w dy_copy - w (mean terms)), reached in two passes: with the mean terms once, then w - 1 times
+        # more.  Where the identical rows dominate the batch (every molecule's zero token rows in SimSiam's LLM projector), dy_copy
+        # nearly equals the mean terms and the value between the passes is ~w times the result: rounded to bf16 there, it cost the
+        # first Linear's weight gradient 2-3 % of its direction at w = 48 (cosine against the all-rows form 0.971, against fp32
+        # 0.978 where the all-rows form has 0.991; profiles/capacity_invariance.txt).  With wide_backward (the SimSiam MLPs,
+        # run_mlp) low-precision inputs therefore take both passes in fp32 and round once (block + 8 rows per molecule).
+        # MolecularGCN keeps the two bf16 passes: its figures are those of the flagship step, pinned as they are.
+        low = wide and x.dtype != torch.float32
+        xf = ops.cast(x, torch.float32) if low else x
+        dx, sums = _bn_train_bwd(ops.cast(dy.contiguous(), torch.float32) if low else dy.contiguous(), xf, mean, rstd, g, b, 1.0 / n, relu)
         # tail rows: dx = sum over the w copies of g rstd (dy_copy - mean_dy - xhat mean_dyxhat): the mean terms w times
-        ops.bn_tail_fix(dx, x, mean, rstd, g, sums, 1.0 / n, w, LP, lead)
-        return dx, sums[C:], sums[:C], None, None, None, None, None, None, None, None
+        ops.bn_tail_fix(dx, xf, mean, rstd, g, sums, 1.0 / n, w, LP, lead)
+        if low:
+            dx = ops.cast(dx, x.dtype)
+        return dx, sums[C:], sums[:C], None, None, None, None, None, None, None, None, None
 
 
 class ExpandTailFn(torch.autograd.Function):
@@ -1425,14 +1437,15 @@ class ExpandTailFn(torch.autograd.Function):
         return dy, None, None
 
 
-def batch_norm_rows_weighted_tail(bn: torch.nn.BatchNorm1d, x2d: torch.Tensor, LP: int, lead: int, w: int, relu: bool = False) -> torch.Tensor:
+def batch_norm_rows_weighted_tail(bn: torch.nn.BatchNorm1d, x2d: torch.Tensor, LP: int, lead: int, w: int, relu: bool = False,
+                                  wide_backward: bool = False) -> torch.Tensor:
     """batch_norm_rows for the compact layouts of the drug branch (MolecularGCN; the SimSiam MLPs of the SSL head): inside every
     window of LP rows the rows from `lead` on stand for w identical rows each (training mode; eval mode is row-wise and needs no
     weights)."""
     if not bn.training:
         return batch_norm_rows(bn, x2d, relu=relu)
     y, _mean, _var = BatchNormWeightedTailFn.apply(x2d, *_bn_affine(bn, x2d), bn.running_mean, bn.running_var, bn.eps, bn.momentum,
-                                                 LP, lead, w, relu)
+                                                 LP, lead, w, relu, wide_backward)
     bn_tick(bn.num_batches_tracked)
     return y
 
@@ -1510,7 +1523,7 @@ def run_mlp(seq, x: torch.Tensor, tail=None) -> torch.Tensor:
                 x = x[:, :layer.num_features].contiguous()
             fuse = i + 1 < len(layers) and isinstance(layers[i + 1], nn.ReLU)          # BatchNorm1d -> ReLU: one kernel each way
             if tail is not None and layer.training:
-                x = batch_norm_rows_weighted_tail(layer, x, *tail, relu=fuse)
+                x = batch_norm_rows_weighted_tail(layer, x, *tail, relu=fuse, wide_backward=True)
             else:
                 x = batch_norm_rows(layer, x, relu=fuse)
             i += 1 if fuse else 0
