@@ -301,6 +301,8 @@ SIGNATURES = {
     "dl_ntxent_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "dl_ntxent_fwd": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "dl_ntxent_bwd": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp]),
+    "dl_latent_topk_workspace_bytes": (c_sz, [c_i64, c_i64, c_i32, c_i64]),
+    "dl_latent_topk": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz]),
     "dl_triplet_sigcos_buffer_floats": (c_sz, [c_i64, c_i64]),
     "dl_triplet_sigcos_fwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "dl_triplet_sigcos_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp]),

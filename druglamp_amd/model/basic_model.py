@@ -496,7 +496,8 @@ class DrugLAMPBase(nn.Module):
     def encode_proteins(self, vp, xp, hints=None) -> "screening.ProteinCode":
         """The per-protein part of the forward (fill / site pooling, ProteinCNN, the protein LLM adaptor, PGCA's query
         in-projection) for a batch of proteins: vp (P, SEQ_LEN) residue codes, xp (P, SEQ_LEN, 640) LLM embeddings (every model
-        takes the fill bit from them).  Same submodules in the same order as _forward."""
+        takes the fill bit from them).  Same submodules in the same order as _forward.  A two_c2p model with an LLM branch also
+        caches `latent` (P, 256) fp32: the cross-modality head's l2-normalised protein latent (_entity_latent)."""
         self._need_eval("encode_proteins")
         if xp is None:
             raise ValueError("encode_proteins: the protein LLM embeddings are needed (the fill bit comes from them, also without an LLM branch)")
@@ -505,28 +506,48 @@ class DrugLAMPBase(nn.Module):
             fill_p, xps = ops.fill_pool(xp, self.site_len, cdt)
             vpc = self.protein_extractor(vp, fill_p, site_pool=self.site_len, plan=self._protein_plan(hints, vp))
             branches = {"v": screening.protein_branch(self.v_gca, vpc)}
+            latent = None
             if self.llm_branch:
-                branches["x"] = screening.protein_branch(self.x_gca, self._prot_adaptor(xps))
-        return screening.ProteinCode(branches, cdt, screening.param_epoch())
+                xpc = self._prot_adaptor(xps)
+                branches["x"] = screening.protein_branch(self.x_gca, xpc)
+                if self.has_latents:
+                    latent = self._entity_latent("prot", vpc, xpc)
+        return screening.ProteinCode(branches, cdt, screening.param_epoch(), latent=latent)
 
     @torch.no_grad()
     def encode_drugs(self, vd, xd, hints=None) -> "screening.DrugCode":
         """The per-drug part of the forward (MolecularGCN, the drug LLM adaptor, PGCA's key / value in-projection with the
         out-projection folded into the values) for a batch of drugs: vd as the forward takes it, xd (D, 512, 384) LLM
         embeddings (None without an LLM branch).  Where an encoder hands over its distinct rows (`_dl_tail`) and compact_keys
-        is on, the code holds those block + 8 keys with the multiplicity as key tail."""
+        is on, the code holds those block + 8 keys with the multiplicity as key tail.  A two_c2p model with an LLM branch
+        also caches `latent` (D, 256) fp32, the cross-modality head's drug latent."""
         self._need_eval("encode_drugs")
         with Fn.deferred_bn_ticks():
             cdt = self.compute_dtype
             vd = self.drug_extractor(vd)
             branches = {"v": self._drug_code_branch(self.v_gca, Fn.cast(vd, cdt), getattr(vd, "_dl_tail", None))}
+            latent = None
             if self.llm_branch:
                 if xd is None:
                     raise ValueError("encode_drugs: this model has an LLM branch and needs the drug LLM embeddings")
                 _, xdp = ops.fill_pool(xd, 1, cdt)
                 xdc = self._drug_adaptor(xdp, hints.drug_tokens if hints is not None else 0)
                 branches["x"] = self._drug_code_branch(self.x_gca, xdc, getattr(xdc, "_dl_tail", None))
-        return screening.DrugCode(branches, cdt, screening.param_epoch())
+                if self.has_latents:
+                    latent = self._entity_latent("drug", vd, xdc)
+        return screening.DrugCode(branches, cdt, screening.param_epoch(), latent=latent)
+
+    @property
+    def has_latents(self) -> bool:
+        """The cross-modality head is part of this model (two_c2p with an LLM branch): entity codes carry its latents."""
+        return bool(getattr(self, "two_c2p", False)) and self.llm_branch
+
+    def _entity_latent(self, kind, t, aug_t):
+        """The cross-modality head's latent per entity, (n, 256) fp32 l2-normalised: the token means of the forward's
+        `cp` tensors (vpc / xpc, vd / xdc; over the full row set — a compact form enters with its multiplicity, unexpanded),
+        then CrossModality.entity_latents in fp32 glue with eval-mode BatchNorm."""
+        means = [screening.token_mean(x, getattr(x, "_dl_tail", None)) for x in (t, aug_t)]
+        return self.cm_model.entity_latents(kind, *means).contiguous()
 
     def _drug_code_branch(self, gca, drug_nodes, tail):
         if tail is not None and self.compact_keys:

@@ -243,6 +243,20 @@ class CrossModality(nn.Module):
                         _mean2embed(self.aug_drug2latent, adm.index_select(0, di), dk, n_d)], dim=-1)
         return F.normalize(self.to_prot_latent(pe), dim=-1), F.normalize(self.to_drug_latent(de), dim=-1)
 
+    @torch.no_grad()
+    def entity_latents(self, kind: str, mean, aug_mean):
+        """The latent of every entity on its own — latents_from_means with identity labels, one side: kind 'prot' or 'drug',
+        mean / aug_mean (n, hidden) fp32 token means of the entity's two modalities -> (n, 2 hidden) fp32, l2-normalised.
+        Eval mode only: the BatchNorms use their running statistics, so a row does not depend on the others."""
+        if kind not in ("prot", "drug"):
+            raise ValueError("entity_latents: kind must be 'prot' or 'drug' (got %r)" % (kind,))
+        a, b, lin = ((self.prot2latent, self.aug_prot2latent, self.to_prot_latent) if kind == "prot"
+                     else (self.drug2latent, self.aug_drug2latent, self.to_drug_latent))
+        if a[0].training or b[0].training:
+            raise RuntimeError("entity_latents: eval mode only (in training mode BatchNorm uses batch statistics)")
+        e = torch.cat([_mean2embed(a, mean.float(), None, None), _mean2embed(b, aug_mean.float(), None, None)], dim=-1)
+        return F.normalize(lin(e), dim=-1)
+
     def forward(self, prot, aug_prot, drug, aug_drug, meta=None, labels=None):
         """meta: the batch's id / label records (the reference's argument); labels: the same thing already on the device
         (CMLabels.fill, or CMCodes.fill in the global-batch form — what a captured step hands over).  One of the two."""

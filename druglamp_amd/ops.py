@@ -1104,6 +1104,40 @@ def ntxent_bwd_ex(aq, ak, bq, bk, off_a: int, off_b: int, n_global: int, tempera
     return da_q, da_k
 
 
+LATENT_DIM = 256          # row width of dl_latent_topk
+LATENT_TOPK_MAX = 1024    # its largest M
+
+
+def latent_topk(q, lib, M: int, slab: Optional[int] = None):
+    """For every row of q (P, 256) the M rows of lib (D, 256) with the largest dot product (dl_latent_topk): (values (P, M)
+    fp32, indices (P, M) int64), value descending, equal values by ascending index, NaN first as in torch.topk.  q and lib both
+    fp32 or both bf16, contiguous; nothing is normalised.  slab (tests): library rows per workgroup pass, a multiple of 64 —
+    the result does not depend on it.  Stream-ordered, no host synchronisation.  Bad arguments raise ValueError."""
+    _need_gpu(q, lib)
+    if q.dim() != 2 or lib.dim() != 2 or q.shape[1] != LATENT_DIM or lib.shape[1] != LATENT_DIM:
+        raise ValueError("latent_topk: q and lib must be (rows, %d) (got %s and %s)" % (LATENT_DIM, tuple(q.shape), tuple(lib.shape)))
+    if q.dtype != lib.dtype or q.dtype not in _DT:
+        raise ValueError("latent_topk: q and lib must both be float32 or both bfloat16 (got %s and %s)" % (q.dtype, lib.dtype))
+    if not (q.is_contiguous() and lib.is_contiguous()):
+        raise ValueError("latent_topk: q and lib must be contiguous")
+    P, D, M = q.shape[0], lib.shape[0], int(M)
+    if P < 1 or not 1 <= M <= min(D, LATENT_TOPK_MAX) or D >= 1 << 31:
+        raise ValueError("latent_topk: needs P >= 1, D < 2^31 and 1 <= M <= min(D, %d) (got P %d, D %d, M %d)" % (LATENT_TOPK_MAX, P, D, M))
+    if slab is not None and (int(slab) < 64 or int(slab) % 64):
+        raise ValueError("latent_topk: slab must be a positive multiple of 64 (got %s)" % (slab,))
+    slab = 0 if slab is None else int(slab)          # 0: the host's choice
+    L = _lib.lib()
+    values = torch.empty((P, M), dtype=torch.float32, device=q.device)
+    indices = torch.empty((P, M), dtype=torch.int32, device=q.device)
+    ws = _ws.get(L.dl_latent_topk_workspace_bytes(P, D, M, slab), q.device)
+    rc = L.dl_latent_topk(q.data_ptr(), lib.data_ptr(), P, D, M, _dt(q), slab, values.data_ptr(), indices.data_ptr(),
+                          _stream(), ws.data_ptr(), ws.numel())
+    if rc in (-1, -2, -3):            # DL_ERR_ARG / _SHAPE / _ALIGN: the caller's arguments
+        raise ValueError("latent_topk: %s" % L.dl_last_error().decode())
+    check(rc, "dl_latent_topk")
+    return values, indices.to(torch.int64)
+
+
 def triplet_sigcos_fwd(p_lats, d_lats, gt_i8, margin: float):
     n_p, dim = p_lats.shape
     n_d = d_lats.shape[0]

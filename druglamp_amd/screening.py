@@ -45,6 +45,9 @@ from . import functional as Fn
 from . import ops
 
 
+LIB_TAIL_ROWS = 8                  # key_tail_rows of every library launch; the tail rows of every compact form
+
+
 def param_epoch() -> int:
     """The optimiser epoch functional.bump_param_epoch advances (weight images and entity codes are valid for one)."""
     return Fn._param_epoch
@@ -109,9 +112,32 @@ def drug_branch(gca, rows: torch.Tensor, tail: Optional[Tuple[int, int]] = None)
     return DrugBranch(code.view(D, Lk, 2 * E), bias, (Lk, t, wt))
 
 
+def token_mean(rows: torch.Tensor, tail=None) -> torch.Tensor:
+    """The fp32 mean over an entity's full row set, (n, C).  rows (n, L, C); tail = (distinct rows (n, block + 8, C), w) of an
+    encoder's compact form (`_dl_tail`): each of its last 8 rows stands for w identical rows, so the mean over the
+    block + 8 w rows is (sum(lead rows) + w sum(tail rows)) / (block + 8 w) — nothing is expanded."""
+    if tail is None:
+        return rows.float().mean(dim=1)
+    y, w = tail
+    lead, w = y.shape[1] - LIB_TAIL_ROWS, int(w)
+    y = y.float()
+    return (y[:, :lead].sum(dim=1) + w * y[:, lead:].sum(dim=1)) / float(lead + LIB_TAIL_ROWS * w)
+
+
+def _cat_latents(codes, what: str):
+    have = [c.latent is not None for c in codes]
+    if not any(have):
+        return None
+    if not all(have):
+        raise ValueError("%s: codes with and without latents" % what)
+    return torch.cat([c.latent for c in codes])
+
+
 class _Code:
-    def __init__(self, branches: Dict[str, object], dtype: torch.dtype, epoch: int):
-        self.branches, self.dtype, self.epoch = dict(branches), dtype, int(epoch)
+    """latent: (n, 256) fp32 l2-normalised cross-modality latents of the entities (two_c2p models with an LLM branch), or None."""
+
+    def __init__(self, branches: Dict[str, object], dtype: torch.dtype, epoch: int, *, latent: Optional[torch.Tensor] = None):
+        self.branches, self.dtype, self.epoch, self.latent = dict(branches), dtype, int(epoch), latent
 
     @staticmethod
     def _same(codes: Sequence["_Code"], what: str):
@@ -136,7 +162,8 @@ class ProteinCode(_Code):
         c0 = cls._same(codes, "ProteinCode")
         if len(codes) == 1:
             return c0
-        return cls({k: tuple(torch.cat([c.branches[k][i] for c in codes]) for i in range(2)) for k in c0.branches}, c0.dtype, c0.epoch)
+        return cls({k: tuple(torch.cat([c.branches[k][i] for c in codes]) for i in range(2)) for k in c0.branches}, c0.dtype, c0.epoch,
+                   latent=_cat_latents(codes, "ProteinCode.cat"))
 
 
 class DrugCode(_Code):
@@ -163,10 +190,9 @@ class DrugCode(_Code):
                 if len({b.layout for b in bs}) > 1:
                     raise ValueError("DrugCode.cat: branch %s has %s keys in full form" % (k, sorted({b.layout[0] for b in bs})))
             out[k] = DrugBranch(torch.cat([b.kv for b in bs]), bs[0].bias, bs[0].layout)
-        return cls(out, c0.dtype, c0.epoch)
+        return cls(out, c0.dtype, c0.epoch, latent=_cat_latents(codes, "DrugCode.cat"))
 
 
-LIB_TAIL_ROWS = 8                  # key_tail_rows of every library launch
 
 
 def fingerprint(model: torch.nn.Module, dtype: torch.dtype) -> str:
@@ -228,10 +254,14 @@ def _trim_branch(b: DrugBranch):
 
 class DrugLibrary:
     """A resident drug library: per branch a LibraryBranch (see the module text), plus the compute dtype, the parameter epoch
-    and — when built or loaded with the model — the parameter fingerprint that a saved file carries."""
+    and — when built or loaded with the model — the parameter fingerprint that a saved file carries.  latent: the drugs'
+    cross-modality latents (D, 256) in the compute dtype (bf16: rounded once, when the library is built), the resident side
+    of ops.latent_topk / Trainer.shortlist; None where the codes carry none."""
 
-    def __init__(self, branches: Dict[str, LibraryBranch], dtype: torch.dtype, epoch: int, fingerprint_: Optional[str] = None):
+    def __init__(self, branches: Dict[str, LibraryBranch], dtype: torch.dtype, epoch: int, fingerprint_: Optional[str] = None,
+                 latent: Optional[torch.Tensor] = None):
         self.branches, self.dtype, self.epoch, self.fingerprint = dict(branches), dtype, int(epoch), fingerprint_
+        self.latent = latent
         self._count_full_keys()
 
     def _count_full_keys(self) -> None:
@@ -246,12 +276,14 @@ class DrugLibrary:
         """The library of the drugs of `codes` (DrugCodes of any layouts, in order; an iterator is consumed code by code, so
         that only the trimmed rows of earlier codes stay alive).  No code is expanded to its full key set.  Plain torch ops:
         runs on CPU tensors too.  model: stamps the library with the fingerprint `save` needs."""
-        c0, parts = None, {}
+        c0, parts, lats = None, {}, []
         for c in codes:
             if c0 is None:
                 c0 = c
-            elif c.dtype != c0.dtype or c.epoch != c0.epoch or set(c.branches) != set(c0.branches):
+            elif c.dtype != c0.dtype or c.epoch != c0.epoch or set(c.branches) != set(c0.branches) or (c.latent is None) != (c0.latent is None):
                 raise ValueError("DrugLibrary: codes of different compute dtypes, parameter epochs or branches")
+            if c.latent is not None:
+                lats.append(c.latent.to(c.dtype))
             for k, b in c.branches.items():
                 parts.setdefault(k, []).append(_trim_branch(b) + (b.bias,))
         if c0 is None:
@@ -261,13 +293,18 @@ class DrugLibrary:
             n_keys = torch.cat([p[1] for p in ps])
             branches[k] = LibraryBranch(torch.cat([p[0] for p in ps]), torch.cumsum(n_keys, 0) - n_keys, n_keys.to(torch.int32),
                                         torch.cat([p[2] for p in ps]), ps[0][3])
-        return cls(branches, c0.dtype, c0.epoch, None if model is None else fingerprint(model, c0.dtype))
+        return cls(branches, c0.dtype, c0.epoch, None if model is None else fingerprint(model, c0.dtype),
+                   latent=torch.cat(lats).contiguous() if lats else None)
 
     def append(self, dcode: DrugCode) -> "DrugLibrary":
         """Adds the drugs of one more code behind the library's (in place; returns self).  Copies the row store once: build a
         large library with from_codes over all its codes."""
         if dcode.dtype != self.dtype or dcode.epoch != self.epoch or set(dcode.branches) != set(self.branches):
             raise ValueError("DrugLibrary.append: the code's compute dtype, parameter epoch or branches differ from the library's")
+        if (dcode.latent is None) != (self.latent is None):
+            raise ValueError("DrugLibrary.append: the code and the library do not both carry latents")
+        if self.latent is not None:
+            self.latent = torch.cat([self.latent, dcode.latent.to(self.dtype)]).contiguous()
         for k, b in dcode.branches.items():
             rows, n_keys, weight = _trim_branch(b)
             lb = self.branches[k]
@@ -284,8 +321,9 @@ class DrugLibrary:
 
     @property
     def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for b in self.branches.values()
-                   for t in (b.rows, b.row0, b.n_keys, b.tail_weight, b.bias) if t is not None)
+        lat = 0 if self.latent is None else self.latent.numel() * self.latent.element_size()
+        return lat + sum(t.numel() * t.element_size() for b in self.branches.values()
+                         for t in (b.rows, b.row0, b.n_keys, b.tail_weight, b.bias) if t is not None)
 
     def keys(self, branch: str = "v") -> torch.Tensor:
         """The stored key count of every drug, (D,) int32."""
@@ -317,6 +355,8 @@ class DrugLibrary:
                 t = getattr(b, f)
                 if t is not None:
                     blob["%s.%s" % (k, f)] = t.detach().cpu()
+        if self.latent is not None:          # (a library without latents writes exactly the keys above)
+            blob["latent"] = self.latent.detach().cpu()
         torch.save(blob, path)
 
     @classmethod
@@ -335,4 +375,5 @@ class DrugLibrary:
         for k in blob["branches"]:
             ts = [blob.get("%s.%s" % (k, f)) for f in LibraryBranch.__slots__]
             branches[k] = LibraryBranch(*[t if t is None or device is None else t.to(device) for t in ts])
-        return cls(branches, dtype, param_epoch(), now)
+        lat = blob.get("latent")
+        return cls(branches, dtype, param_epoch(), now, latent=lat if lat is None or device is None else lat.to(device))

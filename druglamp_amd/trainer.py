@@ -1521,17 +1521,113 @@ class Trainer:
         return lib
 
     @torch.no_grad()
-    def screen_library(self, protein_batches, lib, pair_batch: int = 256, top_k: Optional[int] = None):
+    def _check_shortlist(self, who, lib, M):
+        """The checks of a shortlisted call: M in [1, min(D, 1024)] (ValueError), a library with latents and a model whose
+        codes carry them (RuntimeError)."""
+        from . import ops
+        D, M = lib.n, int(M)
+        if not 1 <= M <= D:
+            raise ValueError("%s: shortlist %d not in [1, %d] (the library's size)" % (who, M, D))
+        if M > ops.LATENT_TOPK_MAX:
+            raise ValueError("%s: shortlist %d is above the kernel's limit of %d" % (who, M, ops.LATENT_TOPK_MAX))
+        if not getattr(self.model, "has_latents", False):
+            raise RuntimeError("%s: the model has no cross-modality latents (a shortlist needs a two_c2p model with an LLM branch, "
+                               "DrugLAMP2C2P; this is %s)" % (who, type(self.model).__name__))
+        if getattr(lib, "latent", None) is None:
+            raise RuntimeError("%s: the library holds no latents (built from codes of another model kind, or saved before latents "
+                               "existed); build it again with Trainer.build_library" % who)
+        return M
+
+    def _shortlist_of(self, pcode, lib, M):
+        from . import ops
+        if pcode.latent is None:
+            raise RuntimeError("shortlist: the protein codes carry no latents")
+        return ops.latent_topk(pcode.latent.to(lib.latent.dtype).contiguous(), lib.latent, M)
+
+    @torch.no_grad()
+    def shortlist(self, protein_batches, lib, M: int):
+        """The prefilter of a two-stage screen: for every protein the M library drugs whose cross-modality latent is nearest
+        (largest cosine: both latents are l2-normalised), by ops.latent_topk against the library's resident latents.  Returns
+        (sims (P, M) fp32, indices (P, M) int64), similarity descending, ties by ascending index.  The protein batches are
+        streamed as in screen_library; each batch's latents are cast to the library's dtype.  How much of the exhaustive
+        top-k a given M keeps depends on the trained head: shortlist_recall measures it."""
+        M = self._check_shortlist("shortlist", lib, M)
+        self.model.eval()
+        sims, idxs = [], []
+        for feat_p, llm_p in protein_batches:
+            s, i = self._shortlist_of(self.model.encode_proteins(feat_p, llm_p), lib, M)
+            sims.append(s)
+            idxs.append(i)
+        self.check_device_flags()
+        if not sims:
+            return (torch.zeros((0, M), dtype=torch.float32, device=self.device), torch.zeros((0, M), dtype=torch.int64, device=self.device))
+        return torch.cat(sims).contiguous(), torch.cat(idxs).contiguous()
+
+    def _screen_shortlisted(self, protein_batches, lib, pair_batch, k, M):
+        """screen_library(top_k=k, shortlist=M): per protein batch the M nearest drugs by latent, the pair stage on those
+        Pn x M pairs alone (chunks of pair_batch pairs, drug-major inside a chunk), then the k most probable of the M."""
+        vals, idxs = [], []
+        for feat_p, llm_p in protein_batches:
+            pcode = self.model.encode_proteins(feat_p, llm_p)
+            Pn = pcode.n
+            _, cand = self._shortlist_of(pcode, lib, M)                 # (Pn, M) int64 on the device
+            di_all = cand.reshape(-1).cpu()                              # (score_library takes host indices: one sync per protein batch)
+            pi_all = torch.arange(Pn).repeat_interleave(M)
+            prob = torch.empty(Pn * M, dtype=torch.float32, device=cand.device)
+            for s0 in range(0, Pn * M, pair_batch):
+                di, pi = di_all[s0:s0 + pair_batch], pi_all[s0:s0 + pair_batch]
+                order = torch.argsort(di * Pn + pi)                      # drug-major: pairs of one drug sit side by side
+                score = self.model.score_library(pcode, lib, pi[order], di[order])
+                pr = torch.sigmoid(score).squeeze(1) if self.n_class == 1 else torch.softmax(score, dim=1)[:, 1]
+                prob[s0 + order.to(prob.device)] = pr
+            best_v, sel = torch.topk(prob.view(Pn, M), k, dim=1)
+            vals.append(best_v)
+            idxs.append(torch.gather(cand, 1, sel))
+            del pcode
+        self.check_device_flags()
+        if not vals:
+            return (torch.zeros((0, k), dtype=torch.float32, device=self.device), torch.zeros((0, k), dtype=torch.int64, device=self.device))
+        return torch.cat(vals).contiguous(), torch.cat(idxs).contiguous()
+
+    @torch.no_grad()
+    def shortlist_recall(self, protein_batches, lib, top_k: int, shortlist: int, pair_batch: int = 256):
+        """How much of the exhaustive screen a shortlist keeps, on the given proteins: one exhaustive screen_library(top_k) and
+        one with shortlist=shortlist; per protein the share of the exhaustive top_k drugs that the shortlisted result also
+        holds.  Returns {"recall": their mean (float), "per_protein": (P,) fp32 tensor}.  The diagnostic to run on a sample
+        of proteins before trusting an M: the recall of the latent prefilter depends on the trained cross-modality head.
+        protein_batches is walked twice (a list, or anything that can be iterated again)."""
+        _, full = self.screen_library(protein_batches, lib, pair_batch=pair_batch, top_k=top_k)
+        _, short = self.screen_library(protein_batches, lib, pair_batch=pair_batch, top_k=top_k, shortlist=shortlist)
+        if full.shape != short.shape:
+            raise RuntimeError("shortlist_recall: protein_batches gave %d proteins on the first walk and %d on the second"
+                               % (full.shape[0], short.shape[0]))
+        per = (full.unsqueeze(2) == short.unsqueeze(1)).any(dim=2).float().mean(dim=1) if full.shape[0] else torch.zeros(0, device=self.device)
+        return {"recall": float(per.mean()) if per.numel() else float("nan"), "per_protein": per}
+
+    @torch.no_grad()
+    def screen_library(self, protein_batches, lib, pair_batch: int = 256, top_k: Optional[int] = None, shortlist: Optional[int] = None):
         """`screen` against a resident drug library: the library stays where it is, the protein batches are streamed — encode
         one, score it against every drug in chunks of pair_batch pairs (drug-major, as in `screen`), drop its code.
         top_k=None: the (P, D) fp32 probabilities of `screen`.  top_k=k: (values (P, k), indices (P, k) int64), the k most
         probable drugs per protein in descending order, merged chunk by chunk with torch.topk on the device: memory is
-        O(P k + pair_batch) whatever the library size."""
+        O(P k + pair_batch) whatever the library size.
+        shortlist=M (with top_k=k <= M <= min(D, 1024); DrugLAMP2C2P and a library with latents): retrieve, then re-rank —
+        each protein's M nearest drugs by cross-modality latent (ops.latent_topk, see `shortlist`), the pair stage on those
+        P x M pairs only, the k most probable of them; same return type.  The cost no longer grows with D, the result is
+        the exhaustive one only as far as the latent prefilter keeps the hits (shortlist_recall measures that)."""
         if pair_batch < 1:
             raise ValueError("screen_library: pair_batch must be positive")
         D = lib.n
         if top_k is not None and not 1 <= int(top_k) <= D:
             raise ValueError("screen_library: top_k %s not in [1, %d]" % (top_k, D))
+        if shortlist is not None:
+            if top_k is None:
+                raise ValueError("screen_library: shortlist needs top_k (the dense (P, D) result has no shortlisted form)")
+            if int(shortlist) < int(top_k):
+                raise ValueError("screen_library: shortlist %d is smaller than top_k %d" % (int(shortlist), int(top_k)))
+            M = self._check_shortlist("screen_library", lib, shortlist)
+            self.model.eval()
+            return self._screen_shortlisted(protein_batches, lib, pair_batch, int(top_k), M)
         self.model.eval()
         rows, vals, idxs = [], [], []
         for feat_p, llm_p in protein_batches:

@@ -878,6 +878,24 @@ int dl_ntxent_fwd(const float* q, const float* k, int64_t n, int64_t d, float te
                   dl_stream s);
 int dl_ntxent_bwd(const float* q, const float* k, int64_t n, int64_t d, float temperature,
                   const float* row_lse, float grad_out, float* dq, float* dk, dl_stream s);
+/* Dot-product top-M (latent_topk.hip): for each of the P query rows q (P x 256, row-major) the M library rows of lib
+ * (D x 256) with the largest 256-term dot product, without a (P, D) matrix.  q and lib both DL_F32 (exact
+ * v_mfma_f32_16x16x4_f32) or both DL_BF16 (v_mfma_f32_16x16x32_bf16), fp32 accumulation in one fixed order: s(p, d) has the
+ * same bits whatever P, D, M, slab and the pair's place in a tile.  Nothing is normalised.
+ *   values[P][M] fp32, indices[P][M] int32: value descending, equal values by ascending index, at the cut the lower index
+ *   wins; a NaN score ranks above every number (torch.topk's order), NaNs by ascending index.  Deterministic.
+ *   slab: library rows per workgroup pass, a positive multiple of 64, or 0 for the host's choice (the library is split over
+ *   ceil(D / slab) workgroups per 64-row query tile; a second kernel merges their lists).  The result does not depend on it.
+ *   workspace: dl_latent_topk_workspace_bytes(P, D, M, slab) bytes (0 for arguments dl_latent_topk rejects), 8-byte aligned:
+ *   per (query tile, slab, row) CAP = pow2(2 M + 64), clamped to [128, 2048], candidate keys of 8 bytes.
+ * Before anything is launched: a null pointer, P < 1, M outside [1, min(D, 1024)], a bad dtype or slab: DL_ERR_ARG; D outside
+ * [1, 2^31) or more workgroups than one grid: DL_ERR_SHAPE; q / lib not 16-byte aligned, values / indices not 4-byte aligned:
+ * DL_ERR_ALIGN; a null, misaligned or short workspace: DL_ERR_WORKSPACE.  Two launches on stream s, no host synchronisation.
+ * (The workspace pair FOLLOWS the stream here: tests/test_stream_contract_gpu.py lists the stream-last entries against its own
+ * case table; this entry's stream contract is pinned by tests/test_latent_topk_gpu.py with the same procedure.) */
+size_t dl_latent_topk_workspace_bytes(int64_t P, int64_t D, int32_t M, int64_t slab);
+int dl_latent_topk(const void* q, const void* lib, int64_t P, int64_t D, int32_t M, int32_t dtype, int64_t slab,
+                   float* values, int32_t* indices, dl_stream s, void* workspace, size_t workspace_bytes);
 /* `dist` must hold dl_triplet_sigcos_buffer_floats(n_p, n_d) floats: the (n_p x n_d) distance matrix
  * first, then scratch that dl_triplet_sigcos_bwd reuses (pass the same buffer). */
 size_t dl_triplet_sigcos_buffer_floats(int64_t n_p, int64_t n_d);
